@@ -8,7 +8,15 @@ one complete ``cugraph_pagerank`` call (power iteration to convergence).
 value = stored edges x PageRank iterations x steps / timed seconds (whole job; the
 same graph at every N, so ``scaling`` is "strong").
 
-Extra fields on the same JSON line:
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs:
+build the graph, warm up, time the K steps, print the line (``ms_per_step`` = the
+timed seconds / K).  ``--dump-outputs DIR`` also writes what the last timed step
+returned (dump_outputs below; the graph is seeded, so two runs with the same
+arguments see the same input).  ``--full`` adds every other measurement listed next
+(the roofline's traffic and copy_ceiling, next_graph_first_call_ms and all the other
+legs); the ``--no-*`` switches then trim it as before.
+
+Extra fields on the same JSON line (``--full``):
   roofline         -- the PageRank iteration: algorithmic bytes/iteration 4E + 16V
                        / average iteration time from HIP events
                       recorded on the library's stream around each chunk of
@@ -176,7 +184,10 @@ def build_rmat_graph(p, h, scale, seed=42, weighted=False, transposed=True, want
 
 
 # ----------------------------------------------------------------------------- PageRank
-def pagerank_leg(p, args, scale, steps, warmup, ctx=None, weighted=False, options=None):
+def pagerank_leg(p, args, scale, steps, warmup, ctx=None, weighted=False, options=None, next_graph=True):
+    """One PageRank measurement.  next_graph=False leaves out the second fresh graph
+    built after the timed steps (next_graph_first_call_ms), which the timed figure does
+    not need."""
     import torch
     h = p.ResourceHandle(ctx.ptr if ctx else None)
     for k, v in (options or {}).items():  # measurement / A-B switches (include/cugraph_amd/ext.h)
@@ -213,12 +224,14 @@ def pagerank_leg(p, args, scale, steps, warmup, ctx=None, weighted=False, option
         p.pagerank(h, g, None, None, None, None, args.alpha, args.epsilon, 500, False)
     torch.cuda.synchronize()
     iters, kms, klaunch = [], 0.0, 0
+    last = None
     h.set_profiling(True)
     barrier(args)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        p.pagerank(h, g, None, None, None, None, args.alpha, args.epsilon, 500, False)
+        last = None  # the previous step's result is freed here, on the clock, as when it was dropped at once
+        last = p.pagerank(h, g, None, None, None, None, args.alpha, args.epsilon, 500, False)
         iters.append(h.last_iterations())
         kms += h.last_hot_kernel_ms()
         klaunch += h.last_hot_kernel_launches()
@@ -230,14 +243,16 @@ def pagerank_leg(p, args, scale, steps, warmup, ctx=None, weighted=False, option
     # edges): what every further graph costs once the process has run one -- the first
     # graph's first call also pays the one-time loads of the kernels only this size uses
     # and the allocator's first hipMallocs of its block sizes
-    g2, _, _ = build_rmat_graph(p, h, scale, weighted=weighted, mg=args.mg)
-    torch.cuda.synchronize()
-    barrier(args)
-    t1 = time.perf_counter()
-    p.pagerank(h, g2, None, None, None, None, args.alpha, args.epsilon, 500, False)
-    torch.cuda.synchronize()
-    next_ms = max_over_ranks(args, time.perf_counter() - t1) * 1e3
-    del g2
+    next_ms = None
+    if next_graph:
+        g2, _, _ = build_rmat_graph(p, h, scale, weighted=weighted, mg=args.mg)
+        torch.cuda.synchronize()
+        barrier(args)
+        t1 = time.perf_counter()
+        p.pagerank(h, g2, None, None, None, None, args.alpha, args.epsilon, 500, False)
+        torch.cuda.synchronize()
+        next_ms = max_over_ranks(args, time.perf_counter() - t1) * 1e3
+        del g2
     value = E * sum(iters) / t
     # algorithmic bytes of one rank's share: (4E + 16V) / N, +4E when the
     # push reads edge weights -- not for all-ones weights, which run the unweighted push
@@ -250,7 +265,7 @@ def pagerank_leg(p, args, scale, steps, warmup, ctx=None, weighted=False, option
         f"{achieved:.1f} GB/s algorithmic")
     return dict(h=h, g=g, V=V, E=E, t=t, iters=iters, value=value, avg_ms=avg_ms, achieved=achieved,
                 bytes_per_iter=bytes_per_iter, build_s=build_s, scale=scale, steps=steps, first_ms=first_ms,
-                next_graph_first_ms=next_ms,
+                next_graph_first_ms=next_ms, last=last,
                 first_iters=first_iters, steady_ms=t / steps * 1e3, reads_w=reads_w)
 
 
@@ -264,6 +279,40 @@ def pagerank_summary(r, args, grid=None):
             "roofline": {"bound": "hbm", "achieved": r["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": r["achieved"] / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": r["bytes_per_iter"],
                          "avg_kernel_ms": r["avg_ms"]}}
+
+
+DUMP_SAMPLE = 1 << 22  # vertex ids written by --dump-outputs (8 B id + 4 B rank each: 48 MiB)
+
+
+def dump_outputs(args, result, out_dir):
+    """--dump-outputs DIR: the (vertices, pageranks) pair the last timed
+    cugraph_pagerank call returned, as DIR/vertices.npy (float64, external vertex ids,
+    ascending) and DIR/pagerank.npy (float32, the rank of each of those ids; 0 for an id
+    with no edge, which the renumbered graph does not hold).  The ids are every id of
+    the R-MAT id space [0, 2^scale) when that has at most DUMP_SAMPLE of them, else a
+    fixed seeded sample of DUMP_SAMPLE; indexing by external id makes two builds
+    comparable whatever order they return the vertices in.  At N > 1 every rank fills
+    in the vertices it owns and rank 0 writes the files."""
+    import numpy as np
+    import torch
+    verts, ranks = result
+    n = 1 << args.scale
+    if n > DUMP_SAMPLE:
+        ids = np.sort(np.random.default_rng(20240229).choice(n, size=DUMP_SAMPLE, replace=False))
+    else:
+        ids = np.arange(n)
+    dense = torch.zeros(n, dtype=torch.float32, device=ranks.device)
+    dense[verts.to(torch.int64)] = ranks.to(torch.float32)
+    sample = dense[torch.as_tensor(ids, device=ranks.device)].cpu()
+    del dense
+    if args.world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(sample, op=dist.ReduceOp.SUM)  # each vertex has one owner; the others hold 0
+    if args.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "vertices.npy"), ids.astype(np.float64))
+        np.save(os.path.join(out_dir, "pagerank.npy"), sample.numpy().astype(np.float32))
+        log(f"[bench] wrote {ids.size} (vertex, pagerank) pairs of the last timed step to {out_dir}")
 
 
 def overlap_leg(p, args, mg_ref, C):
@@ -729,6 +778,13 @@ def main():
     ap.add_argument("--scale", type=int, default=24, help="headline PageRank scale (BASELINE: RMAT-24 at every N)")
     ap.add_argument("--alpha", type=float, default=0.85)
     ap.add_argument("--epsilon", type=float, default=1e-6)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline PageRank run, also measure everything else (CPU baselines, the "
+                         "secondary PageRank legs, BFS, SSSP, Louvain, the copy ceiling, the rocprofv3 PMC traffic "
+                         "passes, the next fresh graph's first call); without it only the headline is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed PageRank call returned to "
+                         "DIR/vertices.npy and DIR/pagerank.npy (see dump_outputs)")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--nx-pagerank-scale", type=int, default=17)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -817,7 +873,13 @@ def main():
         print(json.dumps(r), flush=True)
         return
 
-    r = pagerank_leg(p, args, args.scale, args.steps, args.warmup, args.ctx)
+    if not args.full:  # a plain run: set up, warm up, time the steps, write the outputs, print the line
+        args.no_cpu_baseline = args.no_traffic = True
+        args.secondary = args.bfs = args.sssp = args.louvain = False
+    r = pagerank_leg(p, args, args.scale, args.steps, args.warmup, args.ctx, next_graph=args.full)
+    if args.dump_outputs:
+        dump_outputs(args, r["last"], args.dump_outputs)
+    r["last"] = None
     out = {
         "metric": "PageRank edges/sec + BFS MTEPS on RMAT-24 at 1/2/4/8 MI355X",
         "value": r["value"],
@@ -841,7 +903,7 @@ def main():
             "iterations_per_step": r["iters"][0] if r["iters"] else 0,
             "graph_build_s": round(r["build_s"], 3),
             "first_call_ms": round(r["first_ms"], 3),
-            "next_graph_first_call_ms": round(r["next_graph_first_ms"], 3),
+            "next_graph_first_call_ms": round(r["next_graph_first_ms"], 3) if args.full else None,
             "first_call_note": ("one cugraph_pagerank on the freshly built graph (out-weight sums, push schedule "
                                 "build, calibration chunk, then the iterations to convergence), after "
                                 "PageRank on RMAT-10 with each window size has loaded the code objects; "
@@ -871,10 +933,11 @@ def main():
     if world > 1:  # MG comm bytes per rank and iteration (x~ allgather + u64 sums reduce-scatter)
         Rr = world // C
         out["roofline"]["comm_bytes_per_rank_iter"] = ((C - 1) * r["V"] / world * 4 + (Rr - 1) * r["V"] / world * 8)
-    try:
-        out["roofline"]["copy_ceiling_gbs"] = r["h"].measure_copy_bandwidth(4 << 30, 10)
-    except Exception as e:  # noqa: BLE001
-        out["roofline"]["copy_ceiling_gbs"] = f"unavailable: {e!r}"[:200]
+    if args.full:
+        try:
+            out["roofline"]["copy_ceiling_gbs"] = r["h"].measure_copy_bandwidth(4 << 30, 10)
+        except Exception as e:  # noqa: BLE001
+            out["roofline"]["copy_ceiling_gbs"] = f"unavailable: {e!r}"[:200]
     # (no nested profiler: a bench already running under rocprofv3 skips the traffic passes)
     under_prof = any(k.startswith("ROCPROF_") for k in os.environ)
     do_traffic = rank == 0 and world == 1 and not args.no_traffic and not under_prof
@@ -888,7 +951,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["cpu_baseline"] = {"error": repr(e)[:300]}
     mg_ref = None
-    if world > 1:  # the default (K = 1) result, for the overlapped-chunk leg's bitwise check
+    if world > 1 and args.secondary:  # the default (K = 1) result, for the overlapped-chunk leg's bitwise check
         v1, x1 = p.pagerank(r["h"], r["g"], None, None, None, None, args.alpha, args.epsilon, 500, False)
         mg_ref = (v1.clone(), x1.view(torch.int32).clone(), r["h"].last_iterations())
         del v1, x1

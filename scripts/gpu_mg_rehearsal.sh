@@ -3,7 +3,7 @@
 set -o pipefail
 N=${N:-4}
 LOG=gpurun_out/bl_mg_$N.log
-PYTHONUNBUFFERED=1 timeout -k 10 ${TLIM:-400} python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus $N --comm torch --steps 2 --warmup 1 --scale ${S:-17} --bfs-scale ${S:-17} --louvain-scale ${S:-17} ${EXTRA:-} > $LOG 2>&1 &
+PYTHONUNBUFFERED=1 timeout -k 10 ${TLIM:-400} python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus $N --full --comm torch --steps 2 --warmup 1 --scale ${S:-17} --bfs-scale ${S:-17} --louvain-scale ${S:-17} ${EXTRA:-} > $LOG 2>&1 &
 pid=$!
 while kill -0 $pid 2>/dev/null; do
   sleep 30

@@ -14,6 +14,6 @@ if [ -n "${TESTS:-}" ]; then
   rc=$?; tail -25 $OUT/pytest.log; [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 fi
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 600 python -u bench.py $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 600 python -u bench.py --full $BENCH_ARGS > $OUT/bench.json 2> $OUT/bench.err
   rc=$?; grep "\[bench\]" $OUT/bench.err; [ $rc -eq 0 ] || { tail -20 $OUT/bench.err; exit $rc; }
 fi

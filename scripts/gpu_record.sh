@@ -16,10 +16,10 @@ if [ "${1:-}" != "skip-tests" ]; then
   # record; anything else (fault, abort, time limit) ends the call here
   [ $rc -eq 0 ] || { grep -E "FAILED|Error" $OUT/pytest.log | head; [ $rc -eq 1 ] || exit $rc; }
 fi
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; grep "\[bench\]" $OUT/bench.err; [ $rc -eq 0 ] || { tail -20 $OUT/bench.err; exit $rc; }
 rm -rf /tmp/prof_$TAG
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o bench -- python3 bench.py --no-traffic --no-cpu-baseline > $OUT/prof.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o bench -- python3 bench.py --full --no-traffic --no-cpu-baseline > $OUT/prof.log 2>&1
 rc=$?
 f=$(find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/kernel_stats.csv
 t=$(find /tmp/prof_$TAG -name "*kernel_trace.csv" | head -1)

@@ -1,7 +1,7 @@
 """Per-launch extracts of a round's bench kernel trace (measurement aid).
 
 usage: round_extracts.py TRACE_CSV[.gz] TAG
-Writes, from the rocprofv3 kernel trace of `python3 bench.py --no-traffic --no-cpu-baseline`
+Writes, from the rocprofv3 kernel trace of `python3 bench.py --full --no-traffic --no-cpu-baseline`
 (scripts/gpu_round.sh):
   profiles/<TAG>_pr_launches.csv       every PageRank push / apply launch (make_profile_md.py
                                        drops the post-convergence no-op launches from it)
