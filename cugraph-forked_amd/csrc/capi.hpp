@@ -60,6 +60,8 @@ struct tuning_t {
   bool louvain_wide_keys = false;  // 64-bit hash keys below 2^24 ids (tests)
   double sssp_delta    = 0;     // SSSP delta = sssp_delta * average weight / average degree (0: sssp.hip kDeltaScale)
   int sssp_pull        = 0;     // SSSP dense rounds by pull: 0 by size (sssp.hip kPullDiv), -1 never, n: list > part / n
+  int wcc_sample       = 2;     // WCC: neighbours linked per vertex before the giant component is guessed
+                                // (wcc.hip; 0: no guess, every row fully linked)
 };
 
 struct handle_t {
@@ -256,6 +258,11 @@ struct graph_t {
 struct centrality_result_t {
   std::unique_ptr<device_array_t> vertices;
   std::unique_ptr<device_array_t> values;
+};
+
+struct labeling_result_t {  // reference c_api/labeling_result.hpp
+  std::unique_ptr<device_array_t> vertices;
+  std::unique_ptr<device_array_t> labels;  // vertex type, internal ids (wcc.hip)
 };
 
 struct paths_result_t {

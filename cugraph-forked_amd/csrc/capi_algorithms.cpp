@@ -1,5 +1,6 @@
 // libcugraph_c algorithm entry points on the hot path (MI355X build):
-// PageRank, personalised PageRank, BFS, SSSP, Louvain and their result objects.
+// PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components and their
+// result objects.
 //
 // Argument checks and error behaviour follow cpp/src/c_api/{pagerank.cpp:244-304,
 // bfs.cpp:187-230, sssp.cpp:146-190, louvain.cpp:152-190} and the result getters
@@ -28,6 +29,7 @@ void run_hits(handle_t& h, graph_t& g, double eps, size_t max_iter, array_view_t
               array_view_t const* guess_s, bool normalize, bool expensive, hits_result_t& res);
 void run_extract_paths(handle_t& h, graph_t& g, paths_result_t const& pr, array_view_t const* dests,
                        extract_paths_result_t& res);
+void run_wcc(handle_t& h, graph_t& g, bool expensive, labeling_result_t& res);
 void mg_run_pagerank(handle_t& h, graph_t& g, array_view_t const* pow_v, array_view_t const* pow_s,
                      array_view_t const* guess_v, array_view_t const* guess_s, array_view_t const* pers_v,
                      array_view_t const* pers_s, double alpha, double eps, size_t max_iter, bool expensive,
@@ -220,6 +222,66 @@ extern "C" cugraph_type_erased_device_array_view_t* cugraph_paths_result_get_pre
 extern "C" void cugraph_paths_result_free(cugraph_paths_result_t* result)
 {
   delete reinterpret_cast<paths_result_t*>(result);
+}
+
+// ============================================================== connected components
+// (reference c_api/weakly_connected_components.cpp, strongly_connected_components.cpp, labeling_result.cpp)
+extern "C" cugraph_error_code_t cugraph_weakly_connected_components(const cugraph_resource_handle_t* handle,
+                                                                   cugraph_graph_t* graph,
+                                                                   bool_t do_expensive_check,
+                                                                   cugraph_labeling_result_t** result,
+                                                                   cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    // weakly_connected_components_impl.cuh:285-287
+    CGX_INPUT(g.symmetric,
+              "Invalid input argument: input graph should be symmetric for weakly connected components.");
+    CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED,
+                "multi-GPU weakly connected components is not implemented in this build");
+    auto res = std::make_unique<labeling_result_t>();
+    run_wcc(*H(handle), g, do_expensive_check == TRUE, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_labeling_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_error_code_t cugraph_strongly_connected_components(const cugraph_resource_handle_t* handle,
+                                                                     cugraph_graph_t* graph,
+                                                                     bool_t do_expensive_check,
+                                                                     cugraph_labeling_result_t** result,
+                                                                     cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    (void)do_expensive_check;
+    // c_api/strongly_connected_components.cpp:69-70
+    fail(CUGRAPH_NOT_IMPLEMENTED, "SCC Not currently implemented");
+  });
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_labeling_result_get_vertices(
+  cugraph_labeling_result_t* result)
+{
+  return new_view(reinterpret_cast<labeling_result_t*>(result)->vertices.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_labeling_result_get_labels(
+  cugraph_labeling_result_t* result)
+{
+  return new_view(reinterpret_cast<labeling_result_t*>(result)->labels.get());
+}
+
+extern "C" void cugraph_labeling_result_free(cugraph_labeling_result_t* result)
+{
+  delete reinterpret_cast<labeling_result_t*>(result);
 }
 
 // ============================================================== Louvain

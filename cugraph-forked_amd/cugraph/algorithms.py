@@ -219,6 +219,115 @@ def louvain(G, max_iter=100, resolution=1.0):
     return df, q
 
 
+def _is_matrix(G):
+    if isinstance(G, np.ndarray):
+        return True
+    try:
+        import scipy.sparse as sp
+    except ImportError:
+        return False
+    return sp.issparse(G)
+
+
+def _ensure_args(api_name, G, directed, connection, return_labels):
+    """components/connectivity.py:26-64: defaults and argument errors, before any GPU call."""
+    if isinstance(G, Graph) or _is_nx(G):
+        exc_value = "'%s' cannot be specified for a Graph-type input"
+        if directed is not None:
+            raise TypeError(exc_value % "directed")
+        if return_labels is not None:
+            raise TypeError(exc_value % "return_labels")
+        directed = True
+        return_labels = True
+    else:
+        directed = True if directed is None else directed
+        return_labels = True if return_labels is None else return_labels
+    want = {"strongly_connected_components": "strong", "weakly_connected_components": "weak"}.get(api_name)
+    if want is None:
+        raise RuntimeError(f"invalid API name specified (internal): {api_name}")
+    if connection is not None and connection != want:
+        raise TypeError(f"'connection' must be '{want}' for {api_name}()")
+    return directed, want, return_labels
+
+
+def _matrix_graph(M, directed):
+    """A SciPy sparse matrix or a 2-D numpy array as a Graph over its row indices
+    (renumber=False), and its number of rows."""
+    import pandas as pd
+    if isinstance(M, np.ndarray):
+        if M.ndim != 2:
+            raise TypeError("a numpy input must be a 2-D adjacency matrix")
+        s, d = np.nonzero(M)
+    else:
+        coo = M.tocoo()
+        s, d = coo.row, coo.col
+    if M.shape[0] != M.shape[1]:
+        raise ValueError("the adjacency matrix must be square")
+    G = DiGraph() if directed else Graph()
+    if len(s):
+        G.from_pandas_edgelist(pd.DataFrame({"src": np.asarray(s, np.int64), "dst": np.asarray(d, np.int64)}),
+                               "src", "dst", None, renumber=False)
+    return G, int(M.shape[0])
+
+
+def _components(api_name, G, directed, connection, return_labels):
+    import pandas as pd
+    directed, connection, return_labels = _ensure_args(api_name, G, directed, connection, return_labels)
+    if not (isinstance(G, Graph) or _is_nx(G) or _is_matrix(G)):
+        raise TypeError(f"input type {type(G)} is not a supported type.")
+    p = _plc()
+    run = p.weakly_connected_components if connection == "weak" else p.strongly_connected_components
+    nxv = rows = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    elif _is_matrix(G):
+        G, rows = _matrix_graph(G, directed)
+    if G.edgelist is None:  # a matrix without entries
+        if connection == "strong":
+            raise NotImplementedError("SCC Not currently implemented")
+        vertex = labels = np.zeros(0, np.int64)
+    else:
+        if connection == "weak" and G.is_directed():
+            G = G.to_undirected()  # weak connectivity ignores the direction
+        v, lab = run(p.ResourceHandle(), G._plc_graph, False)
+        vertex, labels = v.cpu().numpy(), lab.cpu().numpy()
+    if rows is not None:
+        # rows without entries (trailing ones past the graph's last id too) are singletons
+        out = np.arange(rows, dtype=labels.dtype if len(labels) else np.int32)
+        out[vertex] = labels
+        n_components = int(len(np.unique(out)))
+        return (n_components, out) if return_labels else n_components
+    df = pd.DataFrame({"labels": labels, "vertex": vertex})
+    if nxv is not None:
+        return dict(zip(nxv.label(df["vertex"]), df["labels"]))
+    return df
+
+
+def weakly_connected_components(G, directed=None, connection=None, return_labels=None):
+    """components/connectivity.py:101-192.  Graph: DataFrame ['labels', 'vertex'];
+    NetworkX graph: dict {node: label}; SciPy sparse matrix / 2-D numpy array:
+    (n_components, labels by row index), or n_components with return_labels=False.
+    The label of a vertex is the smallest internal id of its component (the smallest
+    row index for a matrix)."""
+    return _components("weakly_connected_components", G, directed, connection, return_labels)
+
+
+def strongly_connected_components(G, directed=None, connection=None, return_labels=None):
+    """components/connectivity.py:195-287.  Checks its arguments, then raises
+    NotImplementedError as the reference's C API does."""
+    return _components("strongly_connected_components", G, directed, connection, return_labels)
+
+
+def connected_components(G, directed=None, connection="weak", return_labels=None):
+    """components/connectivity.py:290-375."""
+    if connection == "weak":
+        return weakly_connected_components(G, directed, connection, return_labels)
+    if connection == "strong":
+        return strongly_connected_components(G, directed, connection, return_labels)
+    raise ValueError(f"invalid connection type: {connection}, must be either 'strong' or 'weak'")
+
+
 def _max_degree(G):
     import torch
     e = G.edgelist

@@ -5,7 +5,8 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 (graph_properties.pyx:17-35), ``SGGraph``/``MGGraph`` (graphs.pyx:60-330),
 ``pagerank`` (pagerank.pyx:57-224), ``personalized_pagerank``
 (personalized_pagerank.pyx), ``bfs`` (bfs.pyx:59-200), ``sssp`` (sssp.pyx:52-178),
-``louvain`` (louvain.pyx:58-149) -- same argument names, order, return tuples and
+``louvain`` (louvain.pyx:58-149), ``weakly_connected_components``
+(weakly_connected_components.pyx, components/_connectivity.pyx:132-220) -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -22,7 +23,7 @@ from . import comms  # noqa: E402,F401  (multi-GPU communicator contexts)
 
 __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", "MGGraph", "pagerank",
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
-           "louvain", "version"]
+           "louvain", "weakly_connected_components", "strongly_connected_components", "version"]
 
 
 def allocator_stats():
@@ -380,3 +381,71 @@ def louvain_dendrogram(resource_handle, graph, max_level, resolution, do_expensi
     finally:
         _lib.lib.cugraph_heirarchical_clustering_result_free(res)
     return v, c, q, levels
+
+
+def _labeling(api, resource_handle, graph, do_expensive_check):
+    res = ctypes.c_void_p()
+    _lib.call(api, resource_handle.ptr, graph.c_graph_ptr, int(bool(do_expensive_check)), ctypes.byref(res))
+    v, lab = views_to_tensors_owned(resource_handle.ptr, [_lib.lib.cugraph_labeling_result_get_vertices(res),
+                                                          _lib.lib.cugraph_labeling_result_get_labels(res)],
+                                    res, _lib.lib.cugraph_labeling_result_free)
+    return v, lab
+
+
+def _legacy_wcc(offsets, indices, weights, num_verts, num_edges, labels):
+    """components/_connectivity.pyx:132-220: CSR in, ``labels`` (int32, length num_verts)
+    filled in place.  The CSR must hold both directions of every edge."""
+    import numpy as np
+    import torch
+    if num_verts is None or num_edges is None or labels is None:
+        raise TypeError("the CSR form needs offsets, indices, weights, num_verts, num_edges and labels")
+    num_verts, num_edges = int(num_verts), int(num_edges)
+    off = to_device_tensor(offsets).to(torch.int64)
+    idx = to_device_tensor(indices)
+    if off.numel() != num_verts + 1 or idx.numel() < num_edges:
+        raise ValueError("offsets / indices do not match num_verts / num_edges")
+    is_np = isinstance(labels, np.ndarray)
+    if not is_np and not isinstance(labels, torch.Tensor):
+        raise TypeError("labels must be a torch tensor or a numpy array")
+    if (labels.dtype != (np.int32 if is_np else torch.int32)) or len(labels) != num_verts:
+        raise ValueError("labels must be int32 of length num_verts")
+    idx = idx[:num_edges].to(torch.int32)
+    src = torch.repeat_interleave(torch.arange(num_verts, dtype=torch.int32, device=idx.device), off[1:] - off[:-1])
+    out = torch.arange(num_verts, dtype=torch.int32, device=idx.device)  # ids without edges: their own index
+    if num_edges:
+        h = ResourceHandle()
+        g = SGGraph(h, GraphProperties(is_symmetric=True), src, idx, None, store_transposed=False, renumber=False)
+        _, lab = _labeling("cugraph_weakly_connected_components", h, g, False)
+        out[:lab.numel()] = lab
+    if is_np:
+        labels[:] = out.cpu().numpy()
+    else:
+        labels.copy_(out.to(labels.device))
+    return labels
+
+
+def weakly_connected_components(resource_handle, graph=None, do_expensive_check=False, *legacy):
+    """weakly_connected_components.pyx.  Returns (vertices, labels): the label of a
+    vertex is the smallest internal id of its component, so label L names
+    ``vertices[L]`` (and is the smallest vertex id itself when the graph was built
+    with renumber=False).
+
+    The 22.10 CSR form ``weakly_connected_components(offsets, indices, weights,
+    num_verts, num_edges, labels)`` is taken when the first argument is not a
+    ResourceHandle; it fills ``labels`` in place."""
+    if not isinstance(resource_handle, ResourceHandle):
+        if len(legacy) > 3:
+            raise TypeError("too many arguments")
+        args = (resource_handle, graph, do_expensive_check) + legacy + (None,) * (3 - len(legacy))
+        return _legacy_wcc(*args)
+    if legacy:
+        raise TypeError("weakly_connected_components(resource_handle, graph, do_expensive_check)")
+    return _labeling("cugraph_weakly_connected_components", resource_handle, graph, do_expensive_check)
+
+
+def strongly_connected_components(resource_handle, graph=None, do_expensive_check=False, *legacy):
+    """Raises NotImplementedError through the C call, as the reference's C API does
+    (c_api/strongly_connected_components.cpp:69)."""
+    if not isinstance(resource_handle, ResourceHandle):
+        raise NotImplementedError("strongly connected components is not implemented")
+    return _labeling("cugraph_strongly_connected_components", resource_handle, graph, do_expensive_check)

@@ -115,6 +115,11 @@ _proto("cugraph_paths_result_get_vertices", P, P)
 _proto("cugraph_paths_result_get_distances", P, P)
 _proto("cugraph_paths_result_get_predecessors", P, P)
 _proto("cugraph_paths_result_free", None, P)
+_proto("cugraph_weakly_connected_components", c_int, P, P, c_int, PP, PP)
+_proto("cugraph_strongly_connected_components", c_int, P, P, c_int, PP, PP)
+_proto("cugraph_labeling_result_get_vertices", P, P)
+_proto("cugraph_labeling_result_get_labels", P, P)
+_proto("cugraph_labeling_result_free", None, P)
 _proto("cugraph_louvain", c_int, P, P, c_size_t, c_double, c_int, PP, PP)
 _proto("cugraph_heirarchical_clustering_result_get_vertices", P, P)
 _proto("cugraph_heirarchical_clustering_result_get_clusters", P, P)

@@ -8,5 +8,6 @@
 #include <cugraph_c/community_algorithms.h>
 #include <cugraph_c/error.h>
 #include <cugraph_c/graph.h>
+#include <cugraph_c/labeling_algorithms.h>
 #include <cugraph_c/resource_handle.h>
 #include <cugraph_c/traversal_algorithms.h>
