@@ -62,6 +62,8 @@ struct tuning_t {
   int sssp_pull        = 0;     // SSSP dense rounds by pull: 0 by size (sssp.hip kPullDiv), -1 never, n: list > part / n
   int wcc_sample       = 2;     // WCC: neighbours linked per vertex before the giant component is guessed
                                 // (wcc.hip; 0: no guess, every row fully linked)
+  int tc_path          = 0;     // triangle count: 0 an oriented edge goes to a thread or a wave by its row sizes,
+                                // 1 every edge to a thread, 2 every edge to a wave (triangle_count.hip)
 };
 
 struct handle_t {
@@ -227,6 +229,13 @@ struct adjacency_t {
   double sssp_delta = -1;
   int64_t sssp_eL = 0, sssp_eH = 0;
   buffer sssp_offL, sssp_offH, sssp_idxL, sssp_wL, sssp_idxH, sssp_wH, sssp_crowL, sssp_crowH;
+  // Triangle counting (triangle_count.hip): the rows oriented towards the higher-ranked endpoint, built on
+  // the first call.  tc_ooff is the prefix sum of the oriented row sizes; a degree-sorted adjacency needs
+  // nothing else (the oriented row of u is the head of its row, the ids below u), any other one keeps the
+  // oriented entries compacted in tc_oidx
+  int64_t tc_edges = -1;  // oriented edges, -1 = not built yet
+  buffer tc_ooff;         // edge_t[V + 1]
+  buffer tc_oidx;         // vertex_t[tc_edges], ascending within each row (!degree_sorted only)
   pr_push_t pr;  // PageRank windowed-push schedule (pagerank.hip), built on first use
 };
 
@@ -263,6 +272,11 @@ struct centrality_result_t {
 struct labeling_result_t {  // reference c_api/labeling_result.hpp
   std::unique_ptr<device_array_t> vertices;
   std::unique_ptr<device_array_t> labels;  // vertex type, internal ids (wcc.hip)
+};
+
+struct triangle_count_result_t {  // reference c_api/triangle_count.cpp
+  std::unique_ptr<device_array_t> vertices;
+  std::unique_ptr<device_array_t> counts;  // edge type
 };
 
 struct paths_result_t {

@@ -1,6 +1,6 @@
 // libcugraph_c algorithm entry points on the hot path (MI355X build):
-// PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components and their
-// result objects.
+// PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components, triangle
+// counting and their result objects.
 //
 // Argument checks and error behaviour follow cpp/src/c_api/{pagerank.cpp:244-304,
 // bfs.cpp:187-230, sssp.cpp:146-190, louvain.cpp:152-190} and the result getters
@@ -30,6 +30,8 @@ void run_hits(handle_t& h, graph_t& g, double eps, size_t max_iter, array_view_t
 void run_extract_paths(handle_t& h, graph_t& g, paths_result_t const& pr, array_view_t const* dests,
                        extract_paths_result_t& res);
 void run_wcc(handle_t& h, graph_t& g, bool expensive, labeling_result_t& res);
+void run_triangle_count(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
+                        triangle_count_result_t& res);
 void mg_run_pagerank(handle_t& h, graph_t& g, array_view_t const* pow_v, array_view_t const* pow_s,
                      array_view_t const* guess_v, array_view_t const* guess_s, array_view_t const* pers_v,
                      array_view_t const* pers_s, double alpha, double eps, size_t max_iter, bool expensive,
@@ -282,6 +284,50 @@ extern "C" cugraph_type_erased_device_array_view_t* cugraph_labeling_result_get_
 extern "C" void cugraph_labeling_result_free(cugraph_labeling_result_t* result)
 {
   delete reinterpret_cast<labeling_result_t*>(result);
+}
+
+// ============================================================== triangle counting
+// (reference c_api/triangle_count.cpp, community/triangle_count_impl.cuh:152-188)
+extern "C" cugraph_error_code_t cugraph_triangle_count(const cugraph_resource_handle_t* handle,
+                                                      cugraph_graph_t* graph,
+                                                      const cugraph_type_erased_device_array_view_t* start,
+                                                      bool_t do_expensive_check,
+                                                      cugraph_triangle_count_result_t** result,
+                                                      cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED, "multi-GPU triangle_count is not implemented in this build");
+    CGX_INPUT(!start || AV(start)->type == g.vertex_type, "vertex type of graph and start must match");
+    // triangle_count_impl.cuh:154-159
+    CGX_INPUT(g.symmetric, "Invalid input arguments: triangle_count currently supports undirected graphs only.");
+    CGX_INPUT(!g.multigraph, "Invalid input arguments: triangle_count currently does not support multi-graphs.");
+    auto res = std::make_unique<triangle_count_result_t>();
+    run_triangle_count(*H(handle), g, start ? AV(start) : nullptr, do_expensive_check == TRUE, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_triangle_count_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_triangle_count_result_get_vertices(
+  cugraph_triangle_count_result_t* result)
+{
+  return new_view(reinterpret_cast<triangle_count_result_t*>(result)->vertices.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_triangle_count_result_get_counts(
+  cugraph_triangle_count_result_t* result)
+{
+  return new_view(reinterpret_cast<triangle_count_result_t*>(result)->counts.get());
+}
+
+extern "C" void cugraph_triangle_count_result_free(cugraph_triangle_count_result_t* result)
+{
+  delete reinterpret_cast<triangle_count_result_t*>(result);
 }
 
 // ============================================================== Louvain

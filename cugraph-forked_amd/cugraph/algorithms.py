@@ -328,6 +328,38 @@ def connected_components(G, directed=None, connection="weak", return_labels=None
     raise ValueError(f"invalid connection type: {connection}, must be either 'strong' or 'weak'")
 
 
+def triangle_count(G, start_list=None):
+    """community/triangle_count.py:22-99.  Returns DataFrame ['vertex', 'counts']: the
+    number of triangles every vertex (or every vertex of ``start_list``: an int, a list
+    or a Series, in the given order) belongs to.  Undirected graphs only."""
+    import pandas as pd
+    import torch
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    if G.is_directed():
+        raise ValueError("input graph must be undirected")
+    start = None
+    if start_list is not None:
+        if isinstance(start_list, (int, np.integer)) and not isinstance(start_list, bool):
+            start_list = [start_list]
+        if isinstance(start_list, list):
+            start_list = pd.Series(nxv.ids(start_list) if nxv is not None else start_list, dtype=np.int64)
+        elif nxv is not None and isinstance(start_list, pd.Series):
+            start_list = pd.Series(nxv.ids(list(start_list)), dtype=np.int64)
+        if not isinstance(start_list, pd.Series):
+            raise TypeError(f"'start_list' must be either a list or a cudf.Series,"
+                            f"got: {getattr(start_list, 'dtype', type(start_list))}")
+        start = torch.as_tensor(start_list.to_numpy()).to(_vertex_dtype(G)).cuda()
+    p = _plc()
+    vertex, counts = p.triangle_count(p.ResourceHandle(), G._plc_graph, start, False)
+    df = pd.DataFrame({"vertex": vertex.cpu().numpy(), "counts": counts.cpu().numpy()})
+    if nxv is not None:
+        df["vertex"] = nxv.label(df["vertex"])
+    return df
+
+
 def _max_degree(G):
     import torch
     e = G.edgelist

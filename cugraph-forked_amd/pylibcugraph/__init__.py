@@ -6,7 +6,8 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 ``pagerank`` (pagerank.pyx:57-224), ``personalized_pagerank``
 (personalized_pagerank.pyx), ``bfs`` (bfs.pyx:59-200), ``sssp`` (sssp.pyx:52-178),
 ``louvain`` (louvain.pyx:58-149), ``weakly_connected_components``
-(weakly_connected_components.pyx, components/_connectivity.pyx:132-220) -- same argument names, order, return tuples and
+(weakly_connected_components.pyx, components/_connectivity.pyx:132-220), ``triangle_count``
+(triangle_count.pyx:57-60) -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -23,7 +24,8 @@ from . import comms  # noqa: E402,F401  (multi-GPU communicator contexts)
 
 __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", "MGGraph", "pagerank",
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
-           "louvain", "weakly_connected_components", "strongly_connected_components", "version"]
+           "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
+           "version"]
 
 
 def allocator_stats():
@@ -449,3 +451,19 @@ def strongly_connected_components(resource_handle, graph=None, do_expensive_chec
     if not isinstance(resource_handle, ResourceHandle):
         raise NotImplementedError("strongly connected components is not implemented")
     return _labeling("cugraph_strongly_connected_components", resource_handle, graph, do_expensive_check)
+
+
+def triangle_count(resource_handle, graph, start_list, do_expensive_check):
+    """triangle_count.pyx:57-60.  Returns (vertices, counts): every vertex's number of
+    triangles, counts in the graph's edge type.  ``start_list`` (None: every vertex)
+    holds vertex ids of the graph's vertex type; they come back as ``vertices`` in the
+    given order, duplicates kept.  An id that is not in the graph counts 0, or raises
+    ValueError with ``do_expensive_check``."""
+    start = optional_view(start_list)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_triangle_count", resource_handle.ptr, graph.c_graph_ptr, vptr(start),
+              int(bool(do_expensive_check)), ctypes.byref(res))
+    v, c = views_to_tensors_owned(resource_handle.ptr, [_lib.lib.cugraph_triangle_count_result_get_vertices(res),
+                                                        _lib.lib.cugraph_triangle_count_result_get_counts(res)],
+                                  res, _lib.lib.cugraph_triangle_count_result_free)
+    return v, c

@@ -120,6 +120,10 @@ _proto("cugraph_strongly_connected_components", c_int, P, P, c_int, PP, PP)
 _proto("cugraph_labeling_result_get_vertices", P, P)
 _proto("cugraph_labeling_result_get_labels", P, P)
 _proto("cugraph_labeling_result_free", None, P)
+_proto("cugraph_triangle_count", c_int, P, P, P, c_int, PP, PP)
+_proto("cugraph_triangle_count_result_get_vertices", P, P)
+_proto("cugraph_triangle_count_result_get_counts", P, P)
+_proto("cugraph_triangle_count_result_free", None, P)
 _proto("cugraph_louvain", c_int, P, P, c_size_t, c_double, c_int, PP, PP)
 _proto("cugraph_heirarchical_clustering_result_get_vertices", P, P)
 _proto("cugraph_heirarchical_clustering_result_get_clusters", P, P)

@@ -1,6 +1,6 @@
 /*
  * libcugraph_c community entry points on the hot path -- MI355X build.
- * ABI-compatible with the reference cpp/include/cugraph_c/community_algorithms.h:83-136.
+ * ABI-compatible with the reference cpp/include/cugraph_c/community_algorithms.h:35-136.
  */
 #pragma once
 #include <cugraph_c/error.h>
@@ -10,6 +10,36 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+typedef struct { int32_t align_; } cugraph_triangle_count_result_t;
+
+/*
+ * reference community_algorithms.h:54-59 (implementation c_api/triangle_count.cpp,
+ * algorithm community/triangle_count_impl.cuh).  Every vertex's number of triangles in the
+ * underlying simple graph: self-loops and edge weights are ignored.  The graph must be
+ * symmetric and not flagged multigraph.  start (may be NULL: every vertex) holds vertex ids
+ * of the graph's vertex type; the result then lists them in the given order, duplicates
+ * kept.  With do_expensive_check an id that is not in the graph is CUGRAPH_INVALID_INPUT,
+ * without it such an id counts 0.  A count that does not fit a 32-bit edge type is
+ * CUGRAPH_UNSUPPORTED_TYPE_COMBINATION, never a wrapped number.  Single GPU only.
+ */
+cugraph_error_code_t cugraph_triangle_count(const cugraph_resource_handle_t* handle,
+                                            cugraph_graph_t* graph,
+                                            const cugraph_type_erased_device_array_view_t* start,
+                                            bool_t do_expensive_check,
+                                            cugraph_triangle_count_result_t** result,
+                                            cugraph_error_t** error);
+
+/* reference community_algorithms.h:64 -- the graph's vertex ids, or the start ids */
+cugraph_type_erased_device_array_view_t* cugraph_triangle_count_result_get_vertices(
+  cugraph_triangle_count_result_t* result);
+
+/* reference community_algorithms.h:70 -- counts[i] belongs to vertices[i]; edge type */
+cugraph_type_erased_device_array_view_t* cugraph_triangle_count_result_get_counts(
+  cugraph_triangle_count_result_t* result);
+
+/* reference community_algorithms.h:78 */
+void cugraph_triangle_count_result_free(cugraph_triangle_count_result_t* result);
 
 /* [sic] "heirarchical", as in the reference ABI */
 typedef struct { int32_t align_; } cugraph_heirarchical_clustering_result_t;
