@@ -40,6 +40,10 @@ struct tuning_t {
   bool pr_enc          = true;  // x~ as fixed-point words (fp32 single GPU)
   bool pr_hub          = true;  // hub x~ staged in LDS (16K windows)
   int64_t pr_band_cut  = -1;    // banded push source cut (-1: by size, 0: no bands)
+  int pr_perm          = -1;    // x~ layout map of the symmetric packed schedule (pagerank.hip build_x_layout):
+                                // -1 by window size (push_perm_default), 1 on, 0 off
+  int64_t pr_perm_cut  = -1;    // first vertex the map may move (-1: 2^20), rounded up to a whole window
+  int pr_perm_span     = -1;    // windows per range the map permutes within (-1: by window size, 0: the whole tail)
   int pr_share_div     = 0;     // items per push block on average (0: kShareDiv); windows above 1.5x are shared
   bool pr_fast_build   = true;  // symmetric unweighted schedules through one-word keys (else the general build)
   int mg_chunks        = 0;     // MG overlap chunks (0: one chunk, no overlap)
@@ -76,7 +80,9 @@ struct handle_t {
   size_t last_iterations     = 0;
   double last_hot_ms         = 0;
   size_t last_hot_launches   = 0;
-  size_t last_bfs_levels     = 0;
+  int64_t last_pr_stream     = 0;  // single-GPU PageRank: the push schedule's packed stream entries,
+  int64_t last_pr_permuted   = 0;  // and the vertices its x~ layout map moves (0: no map)
+  size_t last_bfs_levels    = 0;
   size_t last_bfs_bottom_up  = 0;
   size_t last_louvain_levels = 0;
   double last_louvain_sweep_bytes = 0;  // MG: average bytes sent per sweep by this rank
@@ -196,6 +202,11 @@ struct pr_push_t {
   int64_t nwin_real = 0;  // real windows (nwin counts the virtual ones)
   buffer win_pub;         // uint32[nwin_real]: items of the window that published this iteration
   buffer carry;           // uint32[nacc]: 32K windows' carry words (push_args::carry), zero between iterations
+  // x~ layout (pagerank.hip build_x_layout; symmetric packed single-GPU schedules): x~ of vertex
+  // v lives at pos[v], pos[v] = v below perm_cut; sources in the stream are positions
+  buffer pos;             // uint32[V], empty: x~[v] at v
+  int64_t perm_cut = 0;   // first vertex that may move (a window multiple), 0 without a map
+  int64_t stream_len = 0; // packed 16-bit stream entries, padding included (0: 32-bit entries)
   // the last call's iteration count (plain calls: no guess, no personalization) with
   // its alpha and epsilon: the first chunk of the next such call (pagerank.hip)
   int last_iters = 0;

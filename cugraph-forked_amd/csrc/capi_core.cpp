@@ -533,6 +533,14 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
     else if (n == "pr_enc") b(t.pr_enc);
     else if (n == "pr_hub") b(t.pr_hub);
     else if (n == "pr_band_cut") t.pr_band_cut = (int64_t)value;
+    else if (n == "pr_perm") {
+      CGX_INPUT(value == -1 || value == 0 || value == 1, "Invalid input argument: pr_perm must be -1, 0 or 1");
+      i32(t.pr_perm);
+    } else if (n == "pr_perm_cut") t.pr_perm_cut = (int64_t)value;
+    else if (n == "pr_perm_span") {
+      CGX_INPUT(value >= -1 && value <= 65536, "Invalid input argument: pr_perm_span must be in [-1, 65536]");
+      i32(t.pr_perm_span);
+    }
     else if (n == "pr_fast_build") b(t.pr_fast_build);
     else if (n == "pr_share_div") i32(t.pr_share_div);
     else if (n == "mg_chunks") i32(t.mg_chunks);
@@ -579,6 +587,12 @@ extern "C" double cugraph_amd_last_hot_kernel_ms(const cugraph_resource_handle_t
 extern "C" size_t cugraph_amd_last_hot_kernel_launches(const cugraph_resource_handle_t* handle)
 {
   return H(handle)->last_hot_launches;
+}
+extern "C" void cugraph_amd_last_pagerank_schedule(const cugraph_resource_handle_t* handle, int64_t* stream_entries,
+                                                   int64_t* permuted_vertices)
+{
+  *stream_entries    = H(handle)->last_pr_stream;
+  *permuted_vertices = H(handle)->last_pr_permuted;
 }
 extern "C" size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle)
 {

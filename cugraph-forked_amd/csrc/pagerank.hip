@@ -97,7 +97,15 @@ struct pr_args {
                                 // exact: the totals are SG's bit for bit) before k_mg_finish
   int enc;          // x~ stored as fixed-point words (enc_fixed; single-GPU fp32 packed push only)
   int fp64;         // (diff, dangling) summed in fp64 (the pull path: user out-weights bound no sum)
+  uint32_t const* pos;  // x~ layout (build_x_layout): x~ of vertex v is stored at pos[v]; nullptr: at v
 };
+
+// where x~ of vertex v lives
+template <typename V, typename E, typename R>
+__device__ __forceinline__ int64_t x_index(pr_args<V, E, R> const& a, int64_t v)
+{
+  return a.pos ? (int64_t)a.pos[v] : v;
+}
 
 // x~ as the push consumes it: the 64-bit fixed-point value RNE(x * 2^52) of an fp32
 // x in [0, 1] written as one 32-bit word, significand M (24 bits) | shift s << 24,
@@ -284,11 +292,12 @@ __device__ __forceinline__ void init_body(pr_args<V, E, R> const& a)
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < a.nv; v += (int64_t)gridDim.x * blockDim.x) {
     R p  = a.pr[v];
     R ow = a.outw[v];
+    int64_t const xi = x_index(a, v);
     if (ow == R(0)) {
       acc_add(dang, (double)p);
-      store_x<R>(a.x_out, v, R(0), a.enc);
+      store_x<R>(a.x_out, xi, R(0), a.enc);
     } else {
-      store_x<R>(a.x_out, v, (R)((double)p / (double)ow), a.enc);
+      store_x<R>(a.x_out, xi, (R)((double)p / (double)ow), a.enc);
     }
   }
   finish_iteration<V, E, R>(a, Acc(0), dang, false);
@@ -367,7 +376,7 @@ __device__ __forceinline__ void vertex_update_from(pr_args<V, E, R> const& a, V 
   R xv = R(0);
   if (ow == R(0)) acc_add(my_dang, (double)nr);
   else xv = (R)((double)nr / (double)ow);
-  store_x<R>(a.x_out, v, xv, a.enc);
+  store_x<R>(a.x_out, x_index(a, (int64_t)v), xv, a.enc);
 }
 
 template <typename V, typename E, typename R, typename Acc = unsigned long long>
@@ -517,6 +526,25 @@ inline int64_t push_band_cut(int64_t n, tuning_t const& tu)
   (void)n;
   return 0;
 }
+
+// x~ layout of the symmetric packed single-GPU schedule (build_x_layout): tuning_t::pr_perm
+// 1 / 0 turns it on / off, -1 picks by window size: on at 16K windows (RMAT-24 0.554-0.558
+// against 0.574-0.595 ms/iteration, same process), off at the others, where it measured
+// within the run-to-run spread (8K windows, RMAT-22: 0.155-0.157 against 0.158-0.164) or
+// short of three times it (32K, RMAT-26: 2.82-2.86 against 2.87-2.88); DESIGN.md §5.
+// pr_perm_span: the windows per range (-1: one, the window-local form; 2, 4 and 8 measured
+// the same at 16K windows, the whole tail -- span 0 -- no gain there).
+inline bool push_perm_on(int win_bits, tuning_t const& tu)
+{
+  if (tu.pr_perm >= 0) return tu.pr_perm != 0;
+  return win_bits == 14;
+}
+inline int push_perm_span(int win_bits, tuning_t const& tu)
+{
+  (void)win_bits;
+  return tu.pr_perm_span >= 0 ? tu.pr_perm_span : 1;
+}
+constexpr int64_t kPermCut = int64_t(1) << 20;  // x~ below it: 4 MB, one XCD's L2
 
 // persistent push blocks: two per CU, one per CU for 16K-destination windows
 inline int push_blocks(int win_bits) { return win_bits >= 14 ? kPushBlocks / 2 : kPushBlocks; }
@@ -1347,6 +1375,17 @@ __global__ __launch_bounds__(256) void k_pr_apply(push_args<V, E, R> sa)
           if (!sa.keep_acc && f[j] && (!sa.win_multi || sa.win_multi[vj >> sa.win_bits])) sa.acc[vj] = 0ull;
         }
         reinterpret_cast<f4_t*>(a.pr)[q] = f4_t{nr[0], nr[1], nr[2], nr[3]};
+        if (a.pos) {  // x~ layout: the four positions in one load; moved vertices store one by one
+          u4_t const p = reinterpret_cast<u4_t const*>(a.pos)[q];  // (a fresh allocation: 16-byte aligned)
+          uint32_t const v4 = (uint32_t)(4 * q);
+          if (p.x != v4 || p.y != v4 + 1 || p.z != v4 + 2 || p.w != v4 + 3) {
+            store_x<R>(a.x_out, p.x, xv[0], a.enc);
+            store_x<R>(a.x_out, p.y, xv[1], a.enc);
+            store_x<R>(a.x_out, p.z, xv[2], a.enc);
+            store_x<R>(a.x_out, p.w, xv[3], a.enc);
+            continue;
+          }
+        }
         if (a.enc)
           reinterpret_cast<u4_t*>(a.x_out)[q] = u4_t{enc_fixed(xv[0]), enc_fixed(xv[1]), enc_fixed(xv[2]), enc_fixed(xv[3])};
         else
@@ -1487,14 +1526,20 @@ __global__ void k_win_starts(uint64_t const* keys, int64_t ne, int64_t nwin, int
 }
 
 // key_p keys of a symmetric graph's out-edges (row = source, index = destination), in
-// the adjacency's source order; rows found per 4096-edge tile as k_edge_rows does
+// the adjacency's source order; rows found per 4096-edge tile as k_edge_rows does.
+// With an x~ layout (poff, inv: build_x_layout) the keys come out in position order
+// instead -- output row p is vertex inv[p]'s row, at poff[p] -- and carry the position as
+// their source, so the window sort still finds them source-ordered.
 template <typename E>
 __global__ __launch_bounds__(256) void k_push_keys_p(E const* off, uint32_t const* idx, int64_t nv, int64_t ne,
-                                                     int wb, int shv, uint32_t cut, int64_t nwin_real, uint64_t* keys)
+                                                     int wb, int shv, uint32_t cut, int64_t nwin_real, uint64_t* keys,
+                                                     E const* poff = nullptr, uint32_t const* inv = nullptr)
 {
   __shared__ int64_t s_r[2];
   __shared__ E s_off[kRowsTile + 1];
   uint32_t const low = (1u << wb) - 1u;
+  E const* const adj_off = off;
+  if (poff) off = poff;
   for (int64_t e0 = (int64_t)blockIdx.x * kRowsTile; e0 < ne; e0 += (int64_t)gridDim.x * kRowsTile) {
     int64_t const e1 = min(e0 + kRowsTile, ne);
     if (threadIdx.x == 0) {
@@ -1520,7 +1565,10 @@ __global__ __launch_bounds__(256) void k_push_keys_p(E const* off, uint32_t cons
       } else {
         r = row_of_edge(off, r0, r1, e);
       }
-      uint32_t const d = idx[e], src = (uint32_t)r;
+      uint32_t const src = (uint32_t)r;
+      int64_t ea         = e;  // the edge in the adjacency
+      if (poff) ea = (int64_t)adj_off[inv[r]] + (e - (int64_t)(staged ? s_off[r - r0] : off[r]));
+      uint32_t const d = idx[ea];
       uint64_t const w = (uint64_t)(d >> wb) + (cut && src >= cut ? (uint64_t)nwin_real : 0ull);
       keys[e]          = (w << shv) | ((uint64_t)src << wb) | (d & low);
     }
@@ -2004,6 +2052,9 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
   int const sb = 32 - wb;
   if (wb != 14 || w || !tu.pr_packed || band_cut >= n_cols) band_cut = 0;
   pp.carry.release();
+  pp.pos.release();  // (the identity layout: build_x_layout is the symmetric packed build's)
+  pp.perm_cut   = 0;
+  pp.stream_len = 0;
   int64_t const nwin_real = std::max<int64_t>(1, (n_rows + (int64_t(1) << wb) - 1) >> wb);
   int64_t const nwin      = band_cut > 0 ? 2 * nwin_real : nwin_real;
   pp.win_bits        = wb;
@@ -2062,7 +2113,8 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
                    (long long)n_rows, (long long)n_cols, (long long)ne, wb, (long long)total);
     if (total <= ne + ne / 2 && (uint64_t)total < (1ull << 32)) {
       uint16_t const pad_code = (uint16_t)(((1u << (16 - wb)) - 1) << wb);  // a jump of 0: no edge
-      pp.packed = true;
+      pp.packed     = true;
+      pp.stream_len = total;
       if (wb == 15) {  // the 32K push's per-destination carry words
         pp.carry.set_stream(s);
         pp.carry.resize(pp.nacc * sizeof(uint32_t));
@@ -2196,6 +2248,80 @@ void sort_window_keys(rocprim::double_buffer<uint64_t>& db, int64_t ne, int shv,
   HIP_CHECK(rocprim::radix_sort_keys<C>(t.data(), tmp, db, (size_t)ne, shv, shv + vbits, s));
 }
 
+// ---- x~ layout (symmetric unweighted packed single-GPU schedules)
+// The gathers that miss L2 are the x~ lines of the tail sources (ids descend by degree:
+// past ~2^20 a 128-B line of 32 consecutive ids is used by few entries spread over many
+// windows).  The layout stores x~ of vertex v at pos[v] instead of v: pos[v] = v below
+// the cut (the hubs and the hub LDS table are untouched); the vertices from the cut on
+// are cut into ranges of `span` windows (0: one range) and ordered inside their range by
+// (largest neighbour window, second largest, id), so sources that feed the same windows
+// share lines.  Rows are sorted, so the two windows are a row's last two entries (a row
+// of one entry: second 0; an empty row: both 0).  A range is a whole number of windows,
+// so with span 1 the fused apply of window W still writes all of W's own x~ lines.  The
+// schedule is built in position space (k_push_keys_p) and the push gathers x[decoded
+// source] unchanged; only the writers of x~ look pos up (x_index).  No sum is added or
+// split: the fixed-point results are the identity layout's bit for bit.
+template <typename E>
+__global__ void k_layout_keys(E const* off, uint32_t const* idx, int64_t cut, int64_t nv, int wb, int vb,
+                              int64_t range_len, uint64_t* keys, uint32_t* ids)
+{
+  int64_t const n = nv - cut;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t const v = cut + i;
+    int64_t const b = (int64_t)off[v], e = (int64_t)off[v + 1];
+    uint64_t const w1 = e > b ? (uint64_t)(idx[e - 1] >> wb) : 0ull;
+    uint64_t const w2 = e - b > 1 ? (uint64_t)(idx[e - 2] >> wb) : 0ull;
+    uint64_t const r  = range_len ? (uint64_t)(i / range_len) : 0ull;
+    keys[i]           = (r << (2 * vb)) | (w1 << vb) | w2;
+    ids[i]            = (uint32_t)v;
+  }
+}
+
+// from the sorted tail: pos, its inverse and the degrees in position order (deg[nv] = 0)
+template <typename E>
+__global__ void k_layout_finish(E const* off, uint32_t const* tail, int64_t cut, int64_t nv, uint32_t* pos,
+                                uint32_t* inv, E* deg)
+{
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p <= nv; p += (int64_t)gridDim.x * blockDim.x) {
+    if (p == nv) {
+      deg[p] = E(0);
+      continue;
+    }
+    int64_t const v = p < cut ? p : (int64_t)tail[p - cut];
+    inv[p]          = (uint32_t)v;
+    pos[v]          = (uint32_t)p;
+    deg[p]          = off[v + 1] - off[v];
+  }
+}
+
+// pos into pp.pos, inv and the offsets of the rows in position order for the key pass
+template <typename E>
+void build_x_layout(hipStream_t s, E const* off, uint32_t const* idx, int64_t nv, int wb, int64_t cut, int span,
+                    pr_push_t& pp, dbuf<uint32_t>& inv, dbuf<E>& poff)
+{
+  int64_t const n    = nv - cut;
+  int64_t const nwin = (nv + (int64_t(1) << wb) - 1) >> wb;
+  int const vb       = std::max(1, bits_for((unsigned long long)std::max<int64_t>(nwin - 1, 1)));
+  int64_t const range_len = span > 0 ? (int64_t)span << wb : 0;
+  int const rb = range_len ? std::max(1, bits_for((unsigned long long)std::max<int64_t>((n - 1) / range_len, 1))) : 0;
+  dbuf<uint64_t> k0(n, s), k1(n, s);
+  dbuf<uint32_t> v0(n, s), v1(n, s);
+  hipLaunchKernelGGL(k_layout_keys<E>, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, off, idx, cut, nv, wb, vb,
+                     range_len, k0.data(), v0.data());
+  CGX_LAUNCH_CHECK();
+  // (stable: equal keys keep their id order)
+  bool const in1 = radix_sort_pairs_db<uint64_t, uint32_t>(k0.data(), k1.data(), v0.data(), v1.data(), (size_t)n, 0,
+                                                           rb + 2 * vb, s);
+  pp.pos.set_stream(s);
+  pp.pos.resize(nv * sizeof(uint32_t));
+  inv.resize(nv, s);
+  poff.resize(nv + 1, s);
+  hipLaunchKernelGGL(k_layout_finish<E>, dim3(grid_for(nv + 1, kBlock, 4096)), dim3(kBlock), 0, s, off,
+                     in1 ? v1.data() : v0.data(), cut, nv, pp.pos.data<uint32_t>(), inv.data(), poff.data());
+  CGX_LAUNCH_CHECK();
+  exclusive_scan<E, E>(poff.data(), poff.data(), (size_t)(nv + 1), s);  // the degrees to offsets, in place
+}
+
 // The packed schedule of a symmetric unweighted graph straight from its adjacency
 // (build_push_from_coo's packed path with key_p keys; same stream, units, bases and
 // items bit for bit): one word per entry through a keys-only sort of the window bits,
@@ -2216,13 +2342,31 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   if (shv + vbits > 64 || (uint64_t)ne >= (1ull << 32) || (uint64_t)nv >= (1ull << 32)) return false;
   key_p const kc{shv, wb, (sbits >= 32 ? ~0ull : ((1ull << sbits) - 1ull))};
   uint32_t const dmax = (1u << (16 - wb)) - 2, pmax = (1u << wb) - 1;
+  // x~ layout: unbanded schedules, from a cut of at least one window (the hub table stays below it)
+  dbuf<uint32_t> inv;
+  dbuf<E> poff;
+  pp.pos.release();
+  pp.perm_cut = 0;
+  if (band_cut == 0 && ne && push_perm_on(wb, tu)) {
+    int64_t const win = int64_t(1) << wb;
+    int64_t cut       = std::min<int64_t>(std::max<int64_t>(tu.pr_perm_cut >= 0 ? tu.pr_perm_cut : kPermCut, 1), nv);
+    cut               = (cut + win - 1) / win * win;
+    if (cut < nv) {
+      build_x_layout<E>(s, off, idx, nv, wb, cut, push_perm_span(wb, tu), pp, inv, poff);
+      pp.perm_cut = cut;
+    }
+  }
   dbuf<uint64_t> kbuf(std::max<int64_t>(ne, 1), s);
   {
     dbuf<uint64_t> k2(std::max<int64_t>(ne, 1), s);
     if (ne) {
       hipLaunchKernelGGL(k_push_keys_p<E>, dim3((unsigned)std::min<int64_t>((ne + kRowsTile - 1) / kRowsTile, 65536)),
-                         dim3(256), 0, s, off, idx, nv, ne, wb, shv, (uint32_t)band_cut, nwin_real, kbuf.data());
+                         dim3(256), 0, s, off, idx, nv, ne, wb, shv, (uint32_t)band_cut, nwin_real, kbuf.data(),
+                         pp.perm_cut ? poff.data() : (E const*)nullptr,
+                         pp.perm_cut ? inv.data() : (uint32_t const*)nullptr);
       CGX_LAUNCH_CHECK();
+      inv.free();
+      poff.free();
       rocprim::double_buffer<uint64_t> db(kbuf.data(), k2.data());
       if (vbits <= 10) sort_window_keys<window_sort_10>(db, ne, shv, vbits, s);
       else sort_window_keys<rocprim::default_config>(db, ne, shv, vbits, s);
@@ -2251,10 +2395,15 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   CGX_LAUNCH_CHECK();
   exclusive_scan<unsigned long long, unsigned long long>(pad.data(), pb.data(), nwin + 1, s);
   int64_t const total = total0 + (int64_t)to_host(pb.data() + nwin, 1, s)[0];
-  if (!(total <= ne + ne / 2 && (uint64_t)total < (1ull << 32))) return false;
-  pp.built     = true;
-  pp.ok        = true;
-  pp.win_bits  = wb;
+  if (!(total <= ne + ne / 2 && (uint64_t)total < (1ull << 32))) {
+    pp.pos.release();
+    pp.perm_cut = 0;
+    return false;
+  }
+  pp.built      = true;
+  pp.ok         = true;
+  pp.stream_len = total;
+  pp.win_bits   = wb;
   pp.nwin      = nwin;
   pp.bands     = band_cut > 0;
   pp.nwin_real = nwin_real;
@@ -2584,6 +2733,9 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   // fp32 packed push: x~ as enc_fixed words (tuning_t::pr_enc = 0: plain floats, A/B)
   a.enc  = push && adj.pr.packed && std::is_same<R, float>::value && h.tune.pr_enc;
   a.fp64 = push ? 0 : 1;
+  a.pos  = push && adj.pr.perm_cut ? adj.pr.pos.data<uint32_t>() : nullptr;  // x~ layout of this schedule
+  h.last_pr_stream   = push ? adj.pr.stream_len : 0;
+  h.last_pr_permuted = push && adj.pr.perm_cut ? nv - adj.pr.perm_cut : 0;
   hipLaunchKernelGGL((k_pr_init<V, E, R>), dim3(nblk_init), dim3(kBlock), 0, s, a);
   CGX_LAUNCH_CHECK();
 

@@ -104,6 +104,14 @@ class ResourceHandle:
         _lib.lib.cugraph_amd_last_louvain_partition(self.c_resource_handle_ptr, ctypes.byref(e), ctypes.byref(g))
         return e.value, g.value
 
+    def last_pagerank_schedule(self):
+        """Push schedule of the last single-GPU PageRank call: (packed 16-bit stream
+        entries, 0 for the other entry formats; vertices whose x~ the layout map moves,
+        0 when the schedule has no map)."""
+        n, m = ctypes.c_int64(), ctypes.c_int64()
+        _lib.lib.cugraph_amd_last_pagerank_schedule(self.c_resource_handle_ptr, ctypes.byref(n), ctypes.byref(m))
+        return n.value, m.value
+
     def measure_copy_bandwidth(self, nbytes=4 << 30, reps=10):
         """HBM ceiling: 16-B-per-lane copy kernel on this handle's stream, GB/s (read + write)."""
         r = _lib.lib.cugraph_amd_measure_copy_bandwidth(self.c_resource_handle_ptr, int(nbytes), int(reps))

@@ -112,6 +112,9 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * constexpr; these select the alternatives DESIGN.md measured, for A/B scripts and
  * the bitwise-equality tests).  Names: pr_win_bits (0 | 12 | 13 | 14 | 15), pr_packed,
  * pr_whole, pr_calib, pr_deal_global, pr_unit_w, pr_fuse, pr_enc, pr_hub, pr_band_cut (-1 | 0 | cut),
+ * pr_perm (x~ layout map of symmetric unweighted single-GPU schedules: 1 | 0 | -1 by window size),
+ * pr_perm_cut (first vertex the map may move, rounded up to a whole window; -1: 2^20), pr_perm_span
+ * (windows per range the map permutes within: 1 window-local | n | 0 the whole tail | -1 by window size),
  * mg_bfs_alpha, mg_bfs_beta, mg_bfs_pipelined (1 | 0), pr_fast_build, pr_share_div (0 | n),
  * mg_chunks, bfs_alpha, bfs_beta, bfs_probe_vec, bfs_head, bfs_res_grid,
  * bfs_probe_grid, bfs_td_cap, louvain_hash, louvain_big_hash, louvain_big_cap,
@@ -125,6 +128,11 @@ cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, c
                                             cugraph_error_t** error);
 double cugraph_amd_last_hot_kernel_ms(const cugraph_resource_handle_t* handle);
 size_t cugraph_amd_last_hot_kernel_launches(const cugraph_resource_handle_t* handle);
+/* PageRank (single GPU): the push schedule of the last call -- its packed 16-bit stream entries (jumps and
+ * padding included; 0 for 32-bit entries or the pull path) and the vertices whose x~ its layout map moves
+ * (0: no map) */
+void cugraph_amd_last_pagerank_schedule(const cugraph_resource_handle_t* handle, int64_t* stream_entries,
+                                        int64_t* permuted_vertices);
 /* BFS: edges examined, levels, top-down/bottom-up steps of the last call */
 size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle);
 size_t cugraph_amd_last_bfs_bottom_up_steps(const cugraph_resource_handle_t* handle);

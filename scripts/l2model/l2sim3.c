@@ -1,5 +1,6 @@
 // Per-XCD dynamic queues + soft lockstep gate within a round (64 consecutive items
 // of an XCD queue); waiting time charged.  tiles file: int64 (e0, e1, xcd) in queue order.
+// args: sources.bin tiles.bin nv unit cap_lines gate round [blocks = 512]
 #include <stdio.h>
 #include <stdlib.h>
 #include <stdint.h>
@@ -19,7 +20,7 @@ int main(int argc, char** argv) {
   f = fopen(argv[2], "rb"); fseek(f, 0, SEEK_END); int64_t nt = ftell(f) / 24; fseek(f, 0, SEEK_SET);
   int64_t* T = malloc(nt * 24); if (fread(T, 24, nt, f) != (size_t)nt) return 1; fclose(f);
   int64_t nv = atoll(argv[3]), unit = atoll(argv[4]), cap = atoll(argv[5]), gate = atoll(argv[6]); int R = atoi(argv[7]);
-  int nb = 512, ls = 5; int64_t nlines = (nv >> ls) + 1;
+  int nb = argc > 8 ? atoi(argv[8]) : 512, ls = 5; /* blocks (256: one per CU, 16K windows) */ int64_t nlines = (nv >> ls) + 1;
   lru c[8]; for (int x = 0; x < 8; ++x) lru_init(&c[x], nlines, cap);
   int64_t* q[8]; int64_t qn[8] = {0}, qh[8] = {0};
   for (int x = 0; x < 8; ++x) q[x] = malloc(nt * 8);

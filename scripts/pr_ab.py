@@ -50,8 +50,10 @@ def main():
                 n += h.last_hot_kernel_launches()
                 it += h.last_iterations()
             h.set_profiling(False)
+            stream, moved = h.last_pagerank_schedule()
             print(f"RMAT-{scale} {arg}: {ms / max(n, 1):.4f} ms/iteration ({it / 5:.0f} iterations, "
-                  f"{E * it / 5 / (ms / 5 * 1e-3) / 1e9:.1f} Gedges/s)", flush=True)
+                  f"{E * it / 5 / (ms / 5 * 1e-3) / 1e9:.1f} Gedges/s; {stream} stream entries, "
+                  f"{moved} vertices moved by the x~ layout)", flush=True)
         finally:
             g = None
             p.trim_device_cache()
