@@ -44,6 +44,10 @@ struct tuning_t {
                                 // -1 by window size (push_perm_default), 1 on, 0 off
   int64_t pr_perm_cut  = -1;    // first vertex the map may move (-1: 2^20), rounded up to a whole window
   int pr_perm_span     = -1;    // windows per range the map permutes within (-1: by window size, 0: the whole tail)
+  int pr_runs          = -1;    // run rows of the symmetric packed schedule (pagerank.hip k_run_flags): whole
+                                // 64-entry rows of one (window, source) stored as slots + one source; -1 by
+                                // window size (push_runs_on), 1 on, 0 off
+  int64_t pr_run_min   = -1;    // shortest run that gives run rows (-1: kRunMin; at least 64)
   int pr_share_div     = 0;     // items per push block on average (0: kShareDiv); windows above 1.5x are shared
   bool pr_fast_build   = true;  // symmetric unweighted schedules through one-word keys (else the general build)
   int mg_chunks        = 0;     // MG overlap chunks (0: one chunk, no overlap)
@@ -82,6 +86,8 @@ struct handle_t {
   size_t last_hot_launches   = 0;
   int64_t last_pr_stream     = 0;  // single-GPU PageRank: the push schedule's packed stream entries,
   int64_t last_pr_permuted   = 0;  // and the vertices its x~ layout map moves (0: no map)
+  int64_t last_pr_run_rows    = 0;  // its run rows (64 entries of one source each, padding rows not counted)
+  int64_t last_pr_run_entries = 0;  // and the entries they hold
   size_t last_bfs_levels    = 0;
   size_t last_bfs_bottom_up  = 0;
   size_t last_louvain_levels = 0;
@@ -207,6 +213,10 @@ struct pr_push_t {
   buffer pos;             // uint32[V], empty: x~[v] at v
   int64_t perm_cut = 0;   // first vertex that may move (a window multiple), 0 without a map
   int64_t stream_len = 0; // packed 16-bit stream entries, padding included (0: 32-bit entries)
+  // run rows (pagerank.hip k_run_flags): whole 64-entry rows of one (window, source) leave the
+  // packed stream; their slots follow it in ent16, in units of their own (push_unit::base < 0)
+  buffer run_src;          // uint32[rows + a unit's]: the source of every row, kRunPad on padding rows
+  int64_t run_rows = 0, run_entries = 0;
   // the last call's iteration count (plain calls: no guess, no personalization) with
   // its alpha and epsilon: the first chunk of the next such call (pagerank.hip)
   int last_iters = 0;

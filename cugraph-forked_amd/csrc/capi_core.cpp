@@ -541,6 +541,13 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value >= -1 && value <= 65536, "Invalid input argument: pr_perm_span must be in [-1, 65536]");
       i32(t.pr_perm_span);
     }
+    else if (n == "pr_runs") {
+      CGX_INPUT(value == -1 || value == 0 || value == 1, "Invalid input argument: pr_runs must be -1, 0 or 1");
+      i32(t.pr_runs);
+    } else if (n == "pr_run_min") {
+      CGX_INPUT(value == -1 || value >= 64, "Invalid input argument: pr_run_min must be -1 or at least 64");
+      t.pr_run_min = (int64_t)value;
+    }
     else if (n == "pr_fast_build") b(t.pr_fast_build);
     else if (n == "pr_share_div") i32(t.pr_share_div);
     else if (n == "mg_chunks") i32(t.mg_chunks);
@@ -593,6 +600,12 @@ extern "C" void cugraph_amd_last_pagerank_schedule(const cugraph_resource_handle
 {
   *stream_entries    = H(handle)->last_pr_stream;
   *permuted_vertices = H(handle)->last_pr_permuted;
+}
+extern "C" void cugraph_amd_last_pagerank_runs(const cugraph_resource_handle_t* handle, int64_t* run_rows,
+                                               int64_t* run_entries)
+{
+  *run_rows    = H(handle)->last_pr_run_rows;
+  *run_entries = H(handle)->last_pr_run_entries;
 }
 extern "C" size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle)
 {

@@ -546,6 +546,23 @@ inline int push_perm_span(int win_bits, tuning_t const& tu)
 }
 constexpr int64_t kPermCut = int64_t(1) << 20;  // x~ below it: 4 MB, one XCD's L2
 
+// Run rows of the symmetric packed single-GPU schedule (k_run_flags, push_body16's run
+// units): tuning_t::pr_runs 1 / 0 turns them on / off, -1 picks by window size; pr_run_min is
+// the shortest run of one (window, source) that gives rows (at least 64, -1: kRunMin).
+// On at 16K windows (RMAT-24: 9.05 -> 8.52 ms per call, twelve interleaved pairs, each 4.2-8.0 %
+// faster); 32K windows are not measured yet and stay off; 8K-window, fp64, 64-bit-id,
+// banded, weighted and MG schedules have no run path whatever the option says.
+// DESIGN.md §5, profiles/pagerank_run_rows.md.
+constexpr int64_t kRunMin = 64;
+inline bool push_runs_on(int win_bits, tuning_t const& tu)
+{
+  if (win_bits == 13) return false;                // (k_pr_push16<13> has no run path: push_body16 kRuns)
+  if (win_bits == 12 && !tu.pr_enc) return false;  // (nor has the 4K-window kernel for plain-float x~)
+  if (tu.pr_runs >= 0) return tu.pr_runs != 0;
+  return win_bits == 14;
+}
+inline int64_t push_run_min(tuning_t const& tu) { return std::max<int64_t>(tu.pr_run_min > 0 ? tu.pr_run_min : kRunMin, 64); }
+
 // persistent push blocks: two per CU, one per CU for 16K-destination windows
 inline int push_blocks(int win_bits) { return win_bits >= 14 ? kPushBlocks / 2 : kPushBlocks; }
 
@@ -557,9 +574,11 @@ constexpr int64_t kShareDiv = 4;
 
 struct push_unit {
   int64_t k0, k1;  // entries [k0, k1)
-  int64_t base;    // source id of offset 0 (the unit's first source)
+  int64_t base;    // source id of offset 0 (the unit's first source); a run unit (rows of one
+                   // source each, push_body16): ~(its first row in push_args::run_src), negative
   int64_t win;     // window
 };
+constexpr uint32_t kRunPad = 0xffffffffu;  // run_src of a row that pads a window's run rows to a whole segment
 
 template <typename V, typename E, typename R>
 struct push_args {
@@ -568,6 +587,7 @@ struct push_args {
   R const* ew;  // entry weights (weighted graphs)
   uint16_t const* ent16;     // packed 16-bit entries (unweighted graphs, see push_body16)
   uint32_t const* seg_base;  // packed: running source before every 512-entry wave segment
+  uint32_t const* run_src;   // run units (push_unit::base < 0): one source per 64-slot row, kRunPad on padding rows
   push_unit const* units;
   int64_t nunits;
   unsigned long long* acc;  // [n_rows] fixed-point sums, zero between iterations
@@ -1117,6 +1137,11 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
   static_assert(kRows == kPerThread, "a wave segment is one unit row per thread");
   // 32K-destination windows (WB = 15) sum in 32-bit LDS words: 128 KB like the 16K
   // windows' 64-bit words, so the 16K-source hub table still fits beside them
+  // run units (below): single-GPU symmetric fp32 schedules with 32-bit ids, unbanded, not at 8K
+  // windows (push_runs_on) -- with the run path the 8K-window kernel, the fp64 plain-x~ and the
+  // 64-bit-id kernels spilled (more) under their register bounds
+  // (at 4K windows with encoded x~ words only: the plain-float kernel spilled 12 B with it)
+  constexpr bool kRuns = WB != 13 && (WB >= 14 || ENC) && !BANDS && sizeof(V) == 4 && std::is_same<R, float>::value;
   constexpr bool kAcc32 = WB == 15;
   using acc_t           = typename std::conditional<kAcc32, uint32_t, unsigned long long>::type;
   __shared__ acc_t acc[kWin];
@@ -1243,35 +1268,108 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
         }
       }
     };
+    // Run units (the item's first units, base < 0): a row is 64 slots of ONE source, so
+    // there is no delta, no scan and no 64-address gather.  Lane j (mod 8) loads row j's
+    // source and then its x~ word; the row's word is read back with v_readlane, decoded once
+    // on the scalar unit, and a lane only masks its slot and adds.  Rows that pad a window's
+    // run rows to a whole segment (kRunPad) are skipped on a uniform branch.  The loop is
+    // unrolled over kDepth units whose slots and sources are in flight (no register is
+    // handed from unit to unit, which would wait for the newest load every unit); the x~
+    // words follow their sources kDepth - kAhead units later.  A loop of its own, so its
+    // registers do not live beside the packed pipeline's; one unit at a time under the
+    // 64-VGPR bound of the 4K-window kernel.  Compiled only into the kernels whose schedules
+    // can hold run units (kRuns, push_runs_on): the others keep the body they had.
+    int64_t um = ua;
+    if constexpr (kRuns) {
+      while (um < ub && units[um].base < 0) ++um;
+      if (um > ua) {
+        constexpr int kDepth = WB < 14 ? 1 : 4;
+        constexpr int kAhead = kDepth / 2;
+        u32x4_t wq[kDepth];
+        uint32_t sq[kDepth];
+        xw_t xq[kDepth];
+        int nq[kDepth];
+        auto issue = [&](int64_t u, int k) {  // slots and row sources of unit u (past the end: the last one, unused)
+          int64_t const uc = u < um ? u : um - 1;
+          nq[k] = u < um ? seg_n(uc) : 0;
+          wq[k] = nt_load(seg_ptr(uc));  // padded: a unit past the stream's end, run_src by a unit's rows
+          sq[k] = nt_load(sa.run_src + (~units[uc].base + wave * kRows + (lane & 7)));
+        };
+        auto issue_x = [&](int k) { xq[k] = x[sq[k] == kRunPad ? 0u : sq[k]]; };
+        auto word_of = [&](xw_t v, int j) {  // lane j's word, wave-uniform
+          static_assert(sizeof(xw_t) == 4, "run rows: fp32 x~ words");
+          return __builtin_bit_cast(xw_t, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+        };
+        auto run_sum = [&](u32x4_t const& w, uint32_t sv, xw_t xv) {
+          [[maybe_unused]] uint32_t lo[kRows], old[kRows];
+          [[maybe_unused]] uint32_t* const cw = kAcc32 ? sa.carry + ((win & kWinMask) << WB) : nullptr;
+#pragma unroll
+          for (int j = 0; j < kRows; ++j) {
+            if constexpr (kAcc32) lo[j] = old[j] = 0u;
+            if ((uint32_t)__builtin_amdgcn_readlane((int)sv, j) == kRunPad) continue;  // wave-uniform
+            unsigned long long fix;
+            if constexpr (ENC) fix = dec_fixed(word_of(xv, j));
+            else fix = fixed_of(word_of(xv, j));
+            uint32_t const slot = entry(w, j);  // (no delta bits in a run row)
+            if constexpr (kAcc32) {  // the packed path's carry logic
+              lo[j]  = (uint32_t)fix;
+              old[j] = atomicAdd(&acc[slot], lo[j]);
+              if (fix >> 32) atomicAdd(cw + slot, (uint32_t)(fix >> 32));
+            } else {
+              atomicAdd(&acc[slot], fix);
+            }
+          }
+          if constexpr (kAcc32) {
+#pragma unroll
+            for (int j = 0; j < kRows; ++j)
+              if (old[j] > ~lo[j]) atomicAdd(cw + entry(w, j), 1u);
+          }
+        };
+#pragma unroll
+        for (int k = 0; k < kDepth; ++k) issue(ua + k, k);
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) issue_x(k);
+        for (int64_t un = ua; un < um; un += kDepth) {
+#pragma unroll
+          for (int k = 0; k < kDepth; ++k) {  // unit un + k, in slot k
+            issue_x((k + kAhead) % kDepth);   // of unit un + k + kAhead
+            if (nq[k] > 0) run_sum(wq[k], sq[k], xq[k]);
+            issue(un + k + kDepth, k);
+          }
+        }
+      }
+    }
     // Software pipeline: the next unit's gathers are issued before this unit is
     // summed into LDS, so two units' gathers are in flight per wave (the push waits
     // on its gathers: SQ_WAIT_ANY 52 % of the wave cycles, issue 9 %), and the entries
     // of the unit after that are prefetched.
-    int64_t const u1 = ua + 1 < ub ? ua + 1 : ua;
-    int nA      = seg_n(ua);
-    int nB      = seg_n(u1);
-    uint32_t bB = __builtin_amdgcn_readfirstlane(sa.seg_base[u1 * kSegsPerUnit + wave]);
-    u32x4_t wA  = nt_load(seg_ptr(ua));  // padded: the stream has a unit past its end
-    u32x4_t wB  = nt_load(seg_ptr(u1));
-    xw_t xA[kRows];
-    if (nA > 0) gather(wA, __builtin_amdgcn_readfirstlane(sa.seg_base[ua * kSegsPerUnit + wave]), xA);
-    for (int64_t un = ua; un < ub; ++un) {
-      bool const actB = un + 1 < ub && nB > 0;  // wave-uniform
-      xw_t xB[kRows];
-      if (actB) gather(wB, bB, xB);
-      int64_t const u2  = un + 2 < ub ? un + 2 : un;
-      int const n2      = seg_n(u2);
-      uint32_t const b2 = sa.seg_base[u2 * kSegsPerUnit + wave];
-      u32x4_t const e2  = nt_load(seg_ptr(u2));
-      __builtin_amdgcn_sched_barrier(0);  // keep the next gathers and the prefetch ahead of the sums
-      if (nA > 0) sum(wA, xA);
-      wA = wB;
+    if (!kRuns || um < ub) {  // (an item of run units only has no packed unit)
+      int64_t const u1 = um + 1 < ub ? um + 1 : um;
+      int nA      = seg_n(um);
+      int nB      = seg_n(u1);
+      uint32_t bB = __builtin_amdgcn_readfirstlane(sa.seg_base[u1 * kSegsPerUnit + wave]);
+      u32x4_t wA  = nt_load(seg_ptr(um));  // padded: the stream has a unit past its end
+      u32x4_t wB  = nt_load(seg_ptr(u1));
+      xw_t xA[kRows];
+      if (nA > 0) gather(wA, __builtin_amdgcn_readfirstlane(sa.seg_base[um * kSegsPerUnit + wave]), xA);
+      for (int64_t un = um; un < ub; ++un) {
+        bool const actB = un + 1 < ub && nB > 0;  // wave-uniform
+        xw_t xB[kRows];
+        if (actB) gather(wB, bB, xB);
+        int64_t const u2  = un + 2 < ub ? un + 2 : un;
+        int const n2      = seg_n(u2);
+        uint32_t const b2 = sa.seg_base[u2 * kSegsPerUnit + wave];
+        u32x4_t const e2  = nt_load(seg_ptr(u2));
+        __builtin_amdgcn_sched_barrier(0);  // keep the next gathers and the prefetch ahead of the sums
+        if (nA > 0) sum(wA, xA);
+        wA = wB;
 #pragma unroll
-      for (int j = 0; j < kRows; ++j) xA[j] = xB[j];
-      nA = actB ? nB : 0;
-      wB = e2;
-      nB = n2;
-      bB = __builtin_amdgcn_readfirstlane(b2);
+        for (int j = 0; j < kRows; ++j) xA[j] = xB[j];
+        nA = actB ? nB : 0;
+        wB = e2;
+        nB = n2;
+        bB = __builtin_amdgcn_readfirstlane(b2);
+      }
     }
     end_item<WB, V, E, R, FUSE, BANDS>(sa, acc, win);
     // (the item id from LDS too: s_item holds it until thread 0 takes the next)
@@ -1282,8 +1380,7 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
       if ((int64_t)k < sa.tl_cap) {
         unsigned long long* r = sa.tl + 1 + 4 * k;
         r[0] = ((unsigned long long)sa.launch << 32) | blockIdx.x;
-        int64_t const iu = s_item;
-        r[1] = ((unsigned long long)(units[sa.items[iu + 1] - 1].k1 - units[sa.items[iu]].k0) << 32) | (unsigned long long)iu;
+        r[1] = (unsigned long long)s_item;  // (its entries: summed over its units by the host)
         r[2] = s_t0;
         r[3] = t_end;
       }
@@ -1796,7 +1893,7 @@ __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t con
     push_unit const u = units[i / kSegsPerUnit];
     int64_t const p   = u.k0 + (i % kSegsPerUnit) * kSegEntries;
     uint32_t base     = 0;
-    if (p < u.k1) {  // a segment never starts in a window's padding
+    if (p < u.k1 && u.base >= 0) {  // a segment never starts in a window's padding; run units have no bases
       int64_t lo = 0, hi = ne - 1;  // first real entry at a packed position >= p
       while (lo < hi) {
         int64_t mid = (lo + hi) >> 1;
@@ -1813,6 +1910,139 @@ __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t con
       base = j < (int64_t)m ? prev + pmax * (uint32_t)j : src - (m ? 0u : (D <= dmax ? D : 0u));
     }
     seg_base[i] = base;
+  }
+}
+
+// ---- run rows (push_body16's run units; k_run_flags)
+// The sorted keys hold (window, source, slot), so a run of equal (window, source) has
+// ascending, distinct slots.  Of a run of L >= tmin keys (tmin >= 64) the first
+// floor(L / 64) * 64 become run rows -- 64 slots and one source per row -- and leave the
+// packed stream; the other L mod 64 keys and every shorter run stay packed.  Both parts
+// keep their order (k_run_split, a stable partition: the packed keys first, the run keys
+// behind them), so the packed pipeline runs unchanged on its part, with deltas and jumps
+// measured between packed neighbours, and every 64 consecutive run keys are one row.  (A
+// multigraph's duplicate edges repeat a slot in a run; nothing here needs them distinct.)
+// k_run_flags writes 1 for a key that stays packed, 0 for a run-row key.  A key is a run-row
+// key when the 64 keys of its row -- counted from its run's first key -- all lie in the
+// run, and the run has tmin keys: two reads once the run's first key is known.  That is the
+// last run head at or before the key: a max-scan over the block's tile, and for the keys in
+// front of the tile's first head one search per tile by wave 0 (64 lanes at stride 1; past
+// those, at stride 512 for as long as all of them match, then at 8 and at 1).  It also
+// counts the tile's packed keys (tile_packed) for k_run_split.
+constexpr int kFlagThreads = 1024, kFlagPer = 4, kFlagTile = kFlagThreads * kFlagPer;
+__global__ __launch_bounds__(kFlagThreads) void k_run_flags(uint64_t const* keys, int64_t ne, int wb, int64_t tmin,
+                                                            uint8_t* stays, uint32_t* tile_packed)
+{
+  __shared__ int64_t s_first0;
+  __shared__ int s_wave[kFlagThreads / 64];
+  __shared__ uint32_t s_packed;
+  int const t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  for (int64_t k0 = blockIdx.x * (int64_t)kFlagTile; k0 < ne; k0 += (int64_t)gridDim.x * kFlagTile) {
+    if (t == 0) s_packed = 0;
+    if (wv == 0) {  // the first key of the run that the tile's first key is in
+      uint64_t const g0 = keys[k0] >> wb;
+      int64_t hi        = k0;  // lowest key known to be in the run
+      auto back = [&](int64_t stride) {  // lanes look stride, 2 stride, ... back: the matches are a prefix of them
+        int64_t const i = hi - stride * (lane + 1);
+        bool const same = i >= 0 && (keys[i] >> wb) == g0;
+        unsigned long long const m = __ballot(same);
+        int const j = m == ~0ull ? 64 : __builtin_ctzll(~m);
+        hi -= stride * j;
+        return j;
+      };
+      if (back(1) == 64) {
+        while (back(512) == 64) {}
+        back(8);
+        back(1);
+      }
+      if (lane == 0) s_first0 = hi;
+    }
+    int64_t const kt = k0 + (int64_t)kFlagPer * t;
+    uint64_t g[kFlagPer];
+    int hl = -1;  // this thread's last run head, as an offset into the tile
+    uint64_t prev = kt > 0 && kt <= ne ? keys[kt - 1] >> wb : 0;
+#pragma unroll
+    for (int i = 0; i < kFlagPer; ++i) {
+      g[i] = kt + i < ne ? keys[kt + i] >> wb : 0;
+      if (kt + i < ne && (kt + i == 0 || g[i] != prev)) hl = kFlagPer * t + i;
+      prev = g[i];
+    }
+    int h = hl;  // inclusive max-scan over the threads
+    for (int d = 1; d < 64; d <<= 1) {
+      int const o = __shfl_up(h, d);
+      if (lane >= d) h = max(h, o);
+    }
+    if (lane == 63) s_wave[wv] = h;
+    __syncthreads();
+    int he = __shfl_up(h, 1);  // exclusive: the last head in the threads before this one
+    if (lane == 0) he = -1;
+    for (int i = 0; i < wv; ++i) he = max(he, s_wave[i]);
+    prev = kt > 0 && kt <= ne ? keys[kt - 1] >> wb : 0;
+#pragma unroll
+    for (int i = 0; i < kFlagPer; ++i) {
+      int64_t const k = kt + i;
+      if (k >= ne) break;
+      if (k == 0 || g[i] != prev) he = kFlagPer * t + i;
+      prev = g[i];
+      int64_t const first = he >= 0 ? k0 + he : s_first0;
+      int64_t const last  = k - ((k - first) & 63) + 63;  // the last key of this key's row
+      bool const row = last < ne && (keys[last] >> wb) == g[i] && first + tmin - 1 < ne && (keys[first + tmin - 1] >> wb) == g[i];
+      stays[k] = row ? 0 : 1;
+      if (!row) atomicAdd(&s_packed, 1u);
+    }
+    __syncthreads();
+    if (t == 0) tile_packed[k0 / kFlagTile] = s_packed;
+  }
+}
+
+// the stable partition by those flags: the packed keys to out[0, npk), the run keys to
+// out[npk, ne), both in order; tile_off = the exclusive prefix of tile_packed
+__global__ __launch_bounds__(kFlagThreads) void k_run_split(uint64_t const* keys, int64_t ne, uint8_t const* stays,
+                                                            uint32_t const* tile_off, int64_t npk, uint64_t* out)
+{
+  __shared__ int s_wave[kFlagThreads / 64];
+  int const t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  for (int64_t k0 = blockIdx.x * (int64_t)kFlagTile; k0 < ne; k0 += (int64_t)gridDim.x * kFlagTile) {
+    int64_t const kt = k0 + (int64_t)kFlagPer * t;
+    int f[kFlagPer], c = 0;  // this thread's packed keys
+#pragma unroll
+    for (int i = 0; i < kFlagPer; ++i) {
+      f[i] = kt + i < ne ? stays[kt + i] : 0;
+      c += f[i];
+    }
+    int h = c;  // inclusive sum over the threads
+    for (int d = 1; d < 64; d <<= 1) {
+      int const o = __shfl_up(h, d);
+      if (lane >= d) h += o;
+    }
+    if (lane == 63) s_wave[wv] = h;
+    __syncthreads();
+    int before = h - c;  // packed keys of the tile before this thread's
+    for (int i = 0; i < wv; ++i) before += s_wave[i];
+    int64_t const off = (int64_t)tile_off[k0 / kFlagTile];
+    int64_t pp = off + before;                                      // next packed position
+    int64_t pr = npk + (k0 - off) + (kFlagPer * t - before);        // next run position
+#pragma unroll
+    for (int i = 0; i < kFlagPer; ++i) {
+      if (kt + i >= ne) break;
+      out[f[i] ? pp++ : pr++] = keys[kt + i];
+    }
+    __syncthreads();
+  }
+}
+
+// run key i of window w goes to row position rnws[w] + (i - rws[w]) of the run stream
+// (rnws: window starts padded to whole segments), stored lane-interleaved like a packed
+// segment; the row's first key writes the row's source
+__global__ void k_run_pack(uint64_t const* rk, int64_t nrk, int64_t const* rws, int64_t const* rnws, key_p kc,
+                           uint16_t* ent_run, uint32_t* run_src)
+{
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nrk; i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t const key = rk[i];
+    int64_t const w    = kc.win(key);
+    int64_t const p    = rnws[w] + (i - rws[w]);
+    ent_run[seg_store_index(p)] = (uint16_t)kc.slot(key);
+    if ((p & 63) == 0) run_src[p >> 6] = kc.src(key);
   }
 }
 
@@ -1889,26 +2119,28 @@ inline void upload_items(hipStream_t s, pr_push_t& pp, std::vector<int64_t> cons
 inline void build_items(hipStream_t s, pr_push_t& pp, push_unit* units, int64_t nunits, bool xcd_queues,
                         tuning_t const& tu)
 {
-  int64_t const ne = nunits ? to_host(&units[nunits - 1].k1, 1, s)[0] : 0;
   // Items and queues.  From 2^22 rows (8K windows): an item is a window's units,
   // or an equal share of a window of more than 1.5 tg entries; groups of
   // kGroupItems consecutive items are dealt to the 8 queues by longest-processing-
   // time on their entries (RMAT-24: 0.986 -> 0.950 ms/iteration, same-box A/B).
   // Below: one queue of tiles of <= 8 units of a window (RMAT-22: the XCD queues
   // measured 0.199 -> 0.216, the last groups' imbalance outweighing the L2 hits).
-  auto hu = to_host(units, nunits, s);
+  // (Entries are summed unit by unit: a window's run units lie apart from its packed units.)
+  auto hu    = to_host(units, nunits, s);
+  int64_t ne = 0;
+  for (auto const& u : hu) ne += u.k1 - u.k0;
   int64_t const div = tu.pr_share_div > 0 ? tu.pr_share_div : kShareDiv;
   int64_t const tg  = std::max<int64_t>(kPushUnit, ne / (push_blocks(pp.win_bits) * div));
   std::vector<int64_t> item_u, item_e;
   for (int64_t u0 = 0; u0 < nunits;) {
     int64_t u1 = u0;
     while (u1 < nunits && hu[u1].win == hu[u0].win) ++u1;
-    int64_t const size = hu[u1 - 1].k1 - hu[u0].k0;
-    int64_t const n    = std::max<int64_t>(1, (size + tg / 2) / tg);
-    int64_t k          = 0;
-    for (int64_t u = u0; u < u1; ++u) {
-      int64_t const done = hu[u].k0 - hu[u0].k0;
-      bool const head    = u == u0 || (xcd_queues ? (k < n && done * n >= k * size) : (u - u0) % kTileUnits == 0);
+    int64_t size = 0;
+    for (int64_t u = u0; u < u1; ++u) size += hu[u].k1 - hu[u].k0;
+    int64_t const n = std::max<int64_t>(1, (size + tg / 2) / tg);
+    int64_t k = 0, done = 0;
+    for (int64_t u = u0; u < u1; done += hu[u].k1 - hu[u].k0, ++u) {
+      bool const head = u == u0 || (xcd_queues ? (k < n && done * n >= k * size) : (u - u0) % kTileUnits == 0);
       if (head) {
         item_u.push_back(u);
         item_e.push_back(0);
@@ -2330,7 +2562,7 @@ void build_x_layout(hipStream_t s, E const* off, uint32_t const* idx, int64_t nv
 // stream would not pack -- nothing built, the caller takes the general path.
 template <typename E, typename CM>
 bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, int64_t ne, int64_t nv, pr_push_t& pp,
-                              tuning_t const& tu, int64_t band_cut, bool wide)
+                              tuning_t const& tu, int64_t band_cut, bool wide, bool runs_ok)
 {
   int const wb = push_win_bits(nv, tu, wide);
   if (wb != 14 || band_cut >= nv) band_cut = 0;
@@ -2373,6 +2605,34 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
       if (db.current() != kbuf.data()) std::swap(kbuf, k2);
     }
   }
+  // run rows (k_run_flags, k_run_split): one stable partition of the sorted keys; from here on
+  // ne counts the packed keys, and the run keys follow them in the buffer.  Without a single
+  // run of tmin the keys stay where they are and the schedule is the one without run rows.
+  int64_t const ne_all     = ne;
+  uint64_t const* rk_first = nullptr;
+  int64_t nrk              = 0;
+  if (band_cut == 0 && ne && runs_ok && push_runs_on(wb, tu)) {
+    int64_t const ntiles = (ne + kFlagTile - 1) / kFlagTile;
+    unsigned const grid  = (unsigned)std::min<int64_t>(ntiles, 1 << 16);
+    dbuf<uint8_t> stays(ne, s);
+    dbuf<uint32_t> tcnt(ntiles + 1, s), toff(ntiles + 1, s);
+    HIP_CHECK(hipMemsetAsync(tcnt.data() + ntiles, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_run_flags, dim3(grid), dim3(kFlagThreads), 0, s, kbuf.data(), ne, wb, push_run_min(tu),
+                       stays.data(), tcnt.data());
+    CGX_LAUNCH_CHECK();
+    exclusive_scan<uint32_t, uint32_t>(tcnt.data(), toff.data(), ntiles + 1, s);
+    int64_t const npk = (int64_t)to_host(toff.data() + ntiles, 1, s)[0];
+    nrk               = ne - npk;
+    if (nrk) {
+      dbuf<uint64_t> pk(ne, s);  // (the block the sort has just freed)
+      hipLaunchKernelGGL(k_run_split, dim3(grid), dim3(kFlagThreads), 0, s, kbuf.data(), ne, stays.data(), toff.data(),
+                         npk, pk.data());
+      CGX_LAUNCH_CHECK();
+      std::swap(kbuf, pk);
+      rk_first = kbuf.data() + npk;
+      ne       = npk;
+    }
+  }
   uint64_t const* keys = kbuf.data();
   dbuf<int64_t> ws(nwin + 1, s);
   hipLaunchKernelGGL(k_win_starts<key_p>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, keys, ne, nwin,
@@ -2395,7 +2655,7 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   CGX_LAUNCH_CHECK();
   exclusive_scan<unsigned long long, unsigned long long>(pad.data(), pb.data(), nwin + 1, s);
   int64_t const total = total0 + (int64_t)to_host(pb.data() + nwin, 1, s)[0];
-  if (!(total <= ne + ne / 2 && (uint64_t)total < (1ull << 32))) {
+  if (!(total + nrk <= ne_all + ne_all / 2 && (uint64_t)total < (1ull << 32))) {  // (of all entries, run rows included)
     pp.pos.release();
     pp.perm_cut = 0;
     return false;
@@ -2424,9 +2684,43 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   pp.nitems = 0;
   pp.packed = true;
   uint16_t const pad_code = (uint16_t)(((1u << (16 - wb)) - 1) << wb);  // a jump of 0: no edge
+  // run stream: after the packed one, from a unit boundary; every window's rows padded to whole
+  // segments (the padding rows' source stays kRunPad); host-side, over the windows
+  std::vector<int64_t> h_rws, h_rnws;
+  int64_t run_off = 0, run_total = 0;
+  pp.run_rows = pp.run_entries = 0;
+  pp.run_src.release();
+  dbuf<int64_t> rws;
+  if (nrk) {
+    rws.resize(nwin + 1, s);
+    hipLaunchKernelGGL(k_win_starts<key_p>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, rk_first,
+                       nrk, nwin, rws.data(), kc);
+    CGX_LAUNCH_CHECK();
+    h_rws = to_host(rws.data(), (size_t)(nwin + 1), s);
+    h_rnws.assign((size_t)(nwin + 1), 0);
+    for (int64_t w = 0; w < nwin; ++w)
+      h_rnws[w + 1] = h_rnws[w] + (h_rws[w + 1] - h_rws[w] + kSegEntries - 1) / kSegEntries * kSegEntries;
+    run_total       = h_rnws[nwin];
+    run_off         = (total + kPushUnit - 1) / kPushUnit * kPushUnit;
+    pp.run_rows     = nrk / 64;
+    pp.run_entries  = nrk;
+  }
+  int64_t const ent_len = (nrk ? run_off + run_total : total) + kPushUnit;  // + a unit: the kernel prefetches whole units
   pp.ent16.set_stream(s);
-  pp.ent16.resize((total + kPushUnit) * sizeof(uint16_t));  // + a unit: the kernel prefetches whole units
-  fill<uint16_t>(pp.ent16.data<uint16_t>(), (size_t)(total + kPushUnit), pad_code, s);
+  pp.ent16.resize(ent_len * sizeof(uint16_t));
+  fill<uint16_t>(pp.ent16.data<uint16_t>(), (size_t)ent_len, pad_code, s);
+  if (nrk) {
+    int64_t const nrows = run_total / 64 + kPushUnit / 64;  // + a unit's rows: short units' idle waves read on
+    pp.run_src.set_stream(s);
+    pp.run_src.resize(nrows * sizeof(uint32_t));
+    fill<uint32_t>(pp.run_src.data<uint32_t>(), (size_t)nrows, kRunPad, s);
+    dbuf<int64_t> rnws(nwin + 1, s);
+    to_device(rnws.data(), h_rnws.data(), h_rnws.size(), s);
+    hipLaunchKernelGGL(k_run_pack, dim3(grid_for(nrk, kBlock, 16384)), dim3(kBlock), 0, s, rk_first, nrk, rws.data(),
+                       rnws.data(), kc, pp.ent16.data<uint16_t>() + run_off, pp.run_src.data<uint32_t>());
+    CGX_LAUNCH_CHECK();
+    HIP_CHECK(hipStreamSynchronize(s));  // (h_rnws is pageable: the copy has read it)
+  }
   if (ne)
     hipLaunchKernelGGL(k_pack16_p<CM>, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys, ne, ws.data(),
                        cm, pb.data(), kc, pmax, pp.ent16.data<uint16_t>());
@@ -2435,21 +2729,43 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   hipLaunchKernelGGL(k_packed_win_starts<CM>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws.data(),
                      cm, pb.data(), nwin, total0, nws.data());
   CGX_LAUNCH_CHECK();
-  dbuf<uint32_t> ucnt(nwin + 1, s), upos(nwin + 1, s);
-  hipLaunchKernelGGL(k_unit_counts, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
-                     ucnt.data());
-  CGX_LAUNCH_CHECK();
-  exclusive_scan<uint32_t, uint32_t>(ucnt.data(), upos.data(), nwin + 1, s);
-  int64_t const nunits = (int64_t)to_host(upos.data() + nwin, 1, s)[0];
+  int64_t nunits   = 0;
+  push_unit* units = nullptr;
   pp.units.set_stream(s);
-  pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
-  push_unit* units = pp.units.data<push_unit>();
-  if (nunits)
-    hipLaunchKernelGGL(k_units_direct, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
-                       upos.data(), nunits, units);
-  CGX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, total);
-  CGX_LAUNCH_CHECK();
+  if (nrk) {
+    // a window's run units, then its packed units (an item is a range of units): on the host,
+    // from the two sets of window starts.  The packed units are what k_units_direct and
+    // k_unit_ends below give for the same starts ([nws[w] + j kPushUnit, the next unit or
+    // window start), base 0): keep the two in step.
+    auto const h_nws = to_host(nws.data(), (size_t)(nwin + 1), s);
+    std::vector<push_unit> hu;
+    for (int64_t w = 0; w < nwin; ++w) {
+      for (int64_t p = h_rnws[w]; p < h_rnws[w + 1]; p += kPushUnit)
+        hu.push_back(push_unit{run_off + p, run_off + std::min<int64_t>(p + kPushUnit, h_rnws[w + 1]), ~(p / 64), w});
+      for (int64_t p = h_nws[w]; p < h_nws[w + 1]; p += kPushUnit)
+        hu.push_back(push_unit{p, std::min<int64_t>(p + kPushUnit, h_nws[w + 1]), 0, w});
+    }
+    nunits = (int64_t)hu.size();
+    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
+    units = pp.units.data<push_unit>();
+    to_device(units, hu.data(), hu.size(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  } else {
+    dbuf<uint32_t> ucnt(nwin + 1, s), upos(nwin + 1, s);
+    hipLaunchKernelGGL(k_unit_counts, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
+                       ucnt.data());
+    CGX_LAUNCH_CHECK();
+    exclusive_scan<uint32_t, uint32_t>(ucnt.data(), upos.data(), nwin + 1, s);
+    nunits = (int64_t)to_host(upos.data() + nwin, 1, s)[0];
+    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
+    units = pp.units.data<push_unit>();
+    if (nunits)
+      hipLaunchKernelGGL(k_units_direct, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
+                         upos.data(), nunits, units);
+    CGX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, total);
+    CGX_LAUNCH_CHECK();
+  }
   pp.seg_base.set_stream(s);
   pp.seg_base.resize(std::max<int64_t>(nunits * kSegsPerUnit, 1) * sizeof(uint32_t));
   if (nunits)
@@ -2467,10 +2783,11 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
 
 template <typename E>
 bool build_push_packed_sym(hipStream_t s, E const* off, uint32_t const* idx, int64_t ne, int64_t nv, pr_push_t& pp,
-                           tuning_t const& tu, int64_t band_cut, bool wide)
+                           tuning_t const& tu, int64_t band_cut, bool wide, bool runs_ok)
 {
-  if (ne < (int64_t(1) << 31)) return build_push_packed_sym_cm<E, uint32_t>(s, off, idx, ne, nv, pp, tu, band_cut, wide);
-  return build_push_packed_sym_cm<E, unsigned long long>(s, off, idx, ne, nv, pp, tu, band_cut, wide);
+  if (ne < (int64_t(1) << 31))
+    return build_push_packed_sym_cm<E, uint32_t>(s, off, idx, ne, nv, pp, tu, band_cut, wide, runs_ok);
+  return build_push_packed_sym_cm<E, unsigned long long>(s, off, idx, ne, nv, pp, tu, band_cut, wide, runs_ok);
 }
 
 template <typename V, typename E, typename R>
@@ -2487,7 +2804,8 @@ void build_pr_push_schedule(handle_t& h, graph_t& g, adjacency_t& adj, bool use_
   if constexpr (sizeof(V) == 4) {
     if (g.symmetric && !use_weights && h.tune.pr_packed && h.tune.pr_fast_build &&
         build_push_packed_sym<E>(s, adj.offsets.data<E>(), reinterpret_cast<uint32_t const*>(adj.indices.data<V>()), ne,
-                                 nv, adj.pr, h.tune, push_band_cut(nv, h.tune), /*wide=*/sizeof(R) == 4))
+                                 nv, adj.pr, h.tune, push_band_cut(nv, h.tune), /*wide=*/sizeof(R) == 4,
+                                 /*runs_ok=*/sizeof(R) == 4))  // (fp32 ranks: push_body16 kRuns)
       return;
   }
   dbuf<uint32_t> rows(std::max<int64_t>(ne, 1), s);
@@ -2549,6 +2867,7 @@ void set_queue_args(push_args<V, E, R>& sa, pr_push_t& pp, hipStream_t s)
   sa.ew       = pp.ew.empty() ? nullptr : pp.ew.data<R>();
   sa.ent16    = pp.ent16.data<uint16_t>();
   sa.seg_base = pp.seg_base.data<uint32_t>();
+  sa.run_src  = pp.run_src.empty() ? nullptr : pp.run_src.data<uint32_t>();
   sa.units    = pp.units.data<push_unit>();
   sa.nunits   = pp.nunits;
   sa.acc      = pp.acc.data<unsigned long long>();
@@ -2731,11 +3050,16 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   a.x_out    = xa.data();
 
   // fp32 packed push: x~ as enc_fixed words (tuning_t::pr_enc = 0: plain floats, A/B)
-  a.enc  = push && adj.pr.packed && std::is_same<R, float>::value && h.tune.pr_enc;
+  // (a 4K-window schedule built with run rows keeps them whatever pr_enc says now: only the
+  // encoded-x~ kernel has the run path at that size, push_body16 kRuns; the bits are the same)
+  a.enc  = push && adj.pr.packed && std::is_same<R, float>::value &&
+          (h.tune.pr_enc || (adj.pr.win_bits == 12 && adj.pr.run_rows > 0));
   a.fp64 = push ? 0 : 1;
   a.pos  = push && adj.pr.perm_cut ? adj.pr.pos.data<uint32_t>() : nullptr;  // x~ layout of this schedule
   h.last_pr_stream   = push ? adj.pr.stream_len : 0;
   h.last_pr_permuted = push && adj.pr.perm_cut ? nv - adj.pr.perm_cut : 0;
+  h.last_pr_run_rows    = push ? adj.pr.run_rows : 0;
+  h.last_pr_run_entries = push ? adj.pr.run_entries : 0;
   hipLaunchKernelGGL((k_pr_init<V, E, R>), dim3(nblk_init), dim3(kBlock), 0, s, a);
   CGX_LAUNCH_CHECK();
 
@@ -2844,8 +3168,10 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
       auto hi = to_host(adj.pr.items.data<int64_t>(), adj.pr.nitems + 1, s);
       for (unsigned long long i = 0; i < n; ++i) {
         unsigned long long const it = rec[4 * i + 1] & 0xffffffffull;
-        std::fprintf(f, "%llu,%llu,%llu,%llu,%lld,%llu,%llu\n", rec[4 * i] >> 32, rec[4 * i] & 0xffffffffull, it,
-                     rec[4 * i + 1] >> 32, (long long)(hu[hi[it]].win & kWinMask), rec[4 * i + 2], rec[4 * i + 3]);
+        long long ents = 0;  // (unit by unit: a window's run units lie apart from its packed units)
+        for (int64_t u = hi[it]; u < hi[it + 1]; ++u) ents += hu[u].k1 - hu[u].k0;
+        std::fprintf(f, "%llu,%llu,%llu,%lld,%lld,%llu,%llu\n", rec[4 * i] >> 32, rec[4 * i] & 0xffffffffull, it, ents,
+                     (long long)(hu[hi[it]].win & kWinMask), rec[4 * i + 2], rec[4 * i + 3]);
       }
       std::fclose(f);
     }

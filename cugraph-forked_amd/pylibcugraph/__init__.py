@@ -112,6 +112,13 @@ class ResourceHandle:
         _lib.lib.cugraph_amd_last_pagerank_schedule(self.c_resource_handle_ptr, ctypes.byref(n), ctypes.byref(m))
         return n.value, m.value
 
+    def last_pagerank_runs(self):
+        """Run rows of the last single-GPU PageRank call's push schedule: (rows of 64
+        entries of one source, the entries they hold); (0, 0) without run rows."""
+        n, m = ctypes.c_int64(), ctypes.c_int64()
+        _lib.lib.cugraph_amd_last_pagerank_runs(self.c_resource_handle_ptr, ctypes.byref(n), ctypes.byref(m))
+        return n.value, m.value
+
     def measure_copy_bandwidth(self, nbytes=4 << 30, reps=10):
         """HBM ceiling: 16-B-per-lane copy kernel on this handle's stream, GB/s (read + write)."""
         r = _lib.lib.cugraph_amd_measure_copy_bandwidth(self.c_resource_handle_ptr, int(nbytes), int(reps))

@@ -115,6 +115,11 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * pr_perm (x~ layout map of symmetric unweighted single-GPU schedules: 1 | 0 | -1 by window size),
  * pr_perm_cut (first vertex the map may move, rounded up to a whole window; -1: 2^20), pr_perm_span
  * (windows per range the map permutes within: 1 window-local | n | 0 the whole tail | -1 by window size),
+ * pr_runs (run rows of symmetric unweighted single-GPU schedules -- whole 64-entry rows of one destination
+ * window and one source, stored as slots plus one source per row: 1 | 0 | -1 by window size; fp32 ranks
+ * and 32-bit ids only, and never at 8K windows (pr_win_bits 13) nor at 4K windows with pr_enc 0: those
+ * kernels have no path for such rows, 1 is then ignored and cugraph_amd_last_pagerank_runs reports 0),
+ * pr_run_min (shortest run that gives such rows, at least 64; -1: the default),
  * mg_bfs_alpha, mg_bfs_beta, mg_bfs_pipelined (1 | 0), pr_fast_build, pr_share_div (0 | n),
  * mg_chunks, bfs_alpha, bfs_beta, bfs_probe_vec, bfs_head, bfs_res_grid,
  * bfs_probe_grid, bfs_td_cap, louvain_hash, louvain_big_hash, louvain_big_cap,
@@ -133,6 +138,10 @@ size_t cugraph_amd_last_hot_kernel_launches(const cugraph_resource_handle_t* han
  * (0: no map) */
 void cugraph_amd_last_pagerank_schedule(const cugraph_resource_handle_t* handle, int64_t* stream_entries,
                                         int64_t* permuted_vertices);
+/* PageRank (single GPU): the run rows of the last call's push schedule (64 entries of one source each;
+ * rows that only pad a window are not counted) and the entries they hold (64 x rows); 0, 0 without them.
+ * These entries are not part of cugraph_amd_last_pagerank_schedule's packed stream. */
+void cugraph_amd_last_pagerank_runs(const cugraph_resource_handle_t* handle, int64_t* run_rows, int64_t* run_entries);
 /* BFS: edges examined, levels, top-down/bottom-up steps of the last call */
 size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle);
 size_t cugraph_amd_last_bfs_bottom_up_steps(const cugraph_resource_handle_t* handle);
