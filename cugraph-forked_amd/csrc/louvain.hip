@@ -32,6 +32,7 @@
 #include "capi.hpp"
 #include "comm.hpp"
 #include "mg_graph.hpp"
+#include "mg_route.hpp"
 #include "prims.hpp"
 
 #include <rocprim/device/device_reduce_by_key.hpp>
@@ -115,21 +116,6 @@ __global__ void k_expand_cols(V const* idx, R const* w, int64_t ne, uint32_t* ds
     ww[e]  = (double)w[e];
   }
 }
-
-// off[v] = first edge with src >= v, v in [0, nv]
-__global__ void k_row_offsets(uint32_t const* src, int64_t ne, int64_t nv, int64_t* off)
-{
-  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v <= nv; v += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = ne;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)src[mid] < v) lo = mid + 1;
-      else hi = mid;
-    }
-    off[v] = lo;
-  }
-}
-
 
 // compact sweep key: row << cb | cluster(destination), cb = bits of the cluster ids,
 // so the radix sort runs over the bits in use only (RMAT-23 level 1: 38 instead of
@@ -273,16 +259,6 @@ __global__ void k_relabel_pairs(u64 const* keys, int64_t n, uint32_t const* nl, 
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = ((u64)nl[(uint32_t)(keys[i] >> 32)] << cb) | (u64)nl[(uint32_t)keys[i]];
-}
-
-// key = s << cb | d (cb = 32 for the plain form)
-__global__ void k_split_pairs(u64 const* keys, int64_t n, uint32_t* s, uint32_t* d, int cb)
-{
-  u64 const mask = cb >= 64 ? ~0ull : (1ull << cb) - 1;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    s[i] = (uint32_t)(keys[i] >> cb);
-    d[i] = (uint32_t)(keys[i] & mask);
-  }
 }
 
 __global__ void k_gather_u32(uint32_t const* table, uint32_t* x, int64_t n)
@@ -1220,8 +1196,6 @@ __global__ void k_walk_totals(int64_t const* cp, uint32_t const* cc, int64_t con
   if (threadIdx.x == 1) tot[1] = bp[n - 1] + (int64_t)bc[n - 1];
 }
 
-inline unsigned blocks(int64_t n) { return grid_for(n > 0 ? n : 1, kBlock, 16384); }
-
 // ---------------------------------------------------------------- driver
 struct louvain_state {
   hipStream_t s;
@@ -1934,9 +1908,7 @@ level_graph contract(louvain_state& S, level_graph const& g, uint32_t* labels)
                        keys2.data());
     CGX_LAUNCH_CHECK();
     radix_sort_pairs<u64, double>(keys2.data(), keys.data(), cw.data(), out.w.data(), (size_t)nce, 0, 2 * cb2, s);
-    hipLaunchKernelGGL(k_split_pairs, dim3(blocks(nce)), dim3(kBlock), 0, s, keys.data(), nce, out.src.data(),
-                       out.dst.data(), cb2);
-    CGX_LAUNCH_CHECK();
+    split_row_keys(keys.data(), nce, out.src.data(), out.dst.data(), s, cb2);
   }
   hipLaunchKernelGGL(k_gather_u32, dim3(blocks(nv)), dim3(kBlock), 0, s, nl.data(), labels, nv);
   CGX_LAUNCH_CHECK();
@@ -2008,8 +1980,7 @@ void louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, 
     iota<uint32_t>(level, nv, 0u, s);
     // vertex weights, cluster keys = every vertex (louvain_impl.cuh:91-103)
     dbuf<int64_t> off(nv + 1, s);
-    hipLaunchKernelGGL(k_row_offsets, dim3(blocks(nv + 1)), dim3(kBlock), 0, s, cur.src.data(), cur.ne, nv, off.data());
-    CGX_LAUNCH_CHECK();
+    lower_bounds(key_of<uint32_t>{cur.src.data()}, cur.ne, target_index{}, nv, off.data(), s);  // first edge of row v
     dbuf<double> k(nv, s), self(nv, s), a(nv, s);
     dbuf<uint8_t> has_edges(nv, s), present(nv, s);
     dbuf<u64> vstats(2, s);
@@ -2141,62 +2112,10 @@ void louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, 
 // which is what the reference's MG test checks level by level
 // (mg_louvain_test.cpp:82-151).
 
-template <typename V>
-__global__ void k_owner_of_src(V const* src, int64_t n, int64_t const* voff, int P, int* dest)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dest[i] = mg_owner_of_global((int64_t)src[i], voff, P);
-}
-
-// first position of rank q's run in a sorted owner array, q = 0..P
-__global__ void k_rank_bounds(int const* sorted, int64_t n, int P, int64_t* out)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (sorted[mid] < q) lo = mid + 1;
-    else hi = mid;
-  }
-  out[q] = lo;
-}
-
-// first position of keys with (key >> 32) >= voff[q], q = 0..P (keys sorted)
-__global__ void k_key_bounds(u64 const* keys, int64_t n, int64_t const* voff, int P, int64_t* out)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  u64 const t = (u64)voff[q] << 32;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < t) lo = mid + 1;
-    else hi = mid;
-  }
-  out[q] = lo;
-}
-
-template <typename V>
-__global__ void k_mg_row_keys(V const* src, V const* dst, int64_t n, int64_t base, u64* keys)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = ((u64)((int64_t)src[i] - base) << 32) | (u64)(uint32_t)dst[i];
-}
-
-
 __global__ void k_new_ids_off(uint32_t const* nmap, int64_t n, uint32_t first, uint32_t* new_of_label)
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     new_of_label[nmap[i]] = first + (uint32_t)i;
-}
-
-std::vector<int64_t> bounds_to_counts(dbuf<int64_t> const& b, int P, hipStream_t s)
-{
-  auto hb = to_host(b.data(), P + 1, s);
-  std::vector<int64_t> c(P);
-  for (int q = 0; q < P; ++q) c[q] = hb[q + 1] - hb[q];
-  return c;
 }
 
 // level 0: the 2D block's edges -> rows of this rank's sources
@@ -2205,78 +2124,41 @@ level_graph mg_level0(handle_t& h, graph_t& g)
 {
   hipStream_t s = h.stream;
   mg_graph_t& mg = *g.mg;
-  comm_t& comm   = *h.mg->world;
-  int const P    = mg.P;
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  int64_t const ne = mg.ne, n1 = std::max<int64_t>(ne, 1);
   // Every temporary is released as soon as its last reader is enqueued (RMAT-26 on one
   // rank: 2.1G edges, 8-16 B each per array)
-  dbuf<int64_t> bnd(P + 1, s), perm(n1, s);
-  {
-    dbuf<int> dest(n1, s), d2(n1, s);
-    dbuf<int64_t> iv(n1, s);
-    if (ne) {
-      hipLaunchKernelGGL(k_owner_of_src<V>, dim3(blocks(ne)), dim3(kBlock), 0, s, mg.src.data<V>(), ne,
-                         voff_d.data(), P, dest.data());
-      CGX_LAUNCH_CHECK();
-      iota<int64_t>(iv.data(), ne, 0, s);
-      if (!radix_sort_pairs_db<int, int64_t>(dest.data(), d2.data(), iv.data(), perm.data(), ne, 0, bits_for(P), s)) {
-        std::swap(dest, d2);  // sorted owners in d2, the permutation in perm
-        std::swap(iv, perm);
-      }
-    }
-    hipLaunchKernelGGL(k_rank_bounds, dim3(1), dim3(256), 0, s, d2.data(), ne, P, bnd.data());
-    CGX_LAUNCH_CHECK();
-  }
-  auto c64 = bounds_to_counts(bnd, P, s);
-  std::vector<size_t> counts(c64.begin(), c64.end()), rc;
-  auto moved = [&](auto const* col, auto tag) {  // one column in owner order, exchanged
-    using T = decltype(tag);
-    dbuf<T> t(n1, s);
-    if (ne) gather<T, int64_t>(t.data(), col, perm.data(), ne, s);
-    return exchange<T>(comm, t.data(), counts, rc, s);
-  };
-  auto rs = moved(mg.src.data<V>(), V{});
-  auto rd = moved(mg.dst.data<V>(), V{});
-  auto rw = moved(mg.w.data<R>(), R{});
-  perm.free();
+  auto e = edges_to_source_owner<V, R>(h, g, /*want_weights=*/true);
   level_graph out;
   out.nv    = g.num_vertices;
   out.base  = mg.voff[mg.p];
   out.nrows = mg.n_own();
-  out.ne    = (int64_t)rs.n;
+  out.ne    = e.n;
   int64_t const m = out.ne, m1 = std::max<int64_t>(m, 1);
   out.src.resize(m1, s);
   out.dst.resize(m1, s);
   out.w.resize(m1, s);
   if (m) {
     dbuf<u64> k1(m, s), k2(m, s);
-    hipLaunchKernelGGL(k_mg_row_keys<V>, dim3(blocks(m)), dim3(kBlock), 0, s, rs.data(), rd.data(), m, out.base,
-                       k1.data());
-    CGX_LAUNCH_CHECK();
-    rs.free();
-    rd.free();
+    row_keys<V>(e.src.data(), e.dst.data(), m, out.base, k1.data(), s);
+    e.src.free();
+    e.dst.free();
     int const kb = 32 + bits_for(std::max<int64_t>(out.nrows - 1, 0));
     bool in1     = false;
     if constexpr (std::is_same_v<R, float>) {
       // fp32 input: the weights are sorted as fp32 and kept beside the fp64 copy, for
       // the level-0 hash sweeps (as the single-GPU level 0 reads the adjacency's)
       dbuf<float> f2(m, s);
-      in1 = radix_sort_pairs_db<u64, float>(k1.data(), k2.data(), rw.data(), f2.data(), (size_t)m, 0, kb, s);
-      out.wfbuf = std::move(in1 ? f2 : rw);
+      in1 = radix_sort_pairs_db<u64, float>(k1.data(), k2.data(), e.w.data(), f2.data(), (size_t)m, 0, kb, s);
+      out.wfbuf = std::move(in1 ? f2 : e.w);
       out.wf    = out.wfbuf.data();
       convert<double, float>(out.w.data(), out.wf, m, s);
     } else {
       dbuf<double> w1(m, s);
-      convert<double, R>(w1.data(), rw.data(), m, s);
-      rw.free();
+      convert<double, R>(w1.data(), e.w.data(), m, s);
+      e.w.free();
       in1 = radix_sort_pairs_db<u64, double>(k1.data(), k2.data(), w1.data(), out.w.data(), (size_t)m, 0, kb, s);
       if (!in1) std::swap(out.w, w1);
     }
-    hipLaunchKernelGGL(k_split_pairs, dim3(blocks(m)), dim3(kBlock), 0, s, in1 ? k2.data() : k1.data(), m,
-                       out.src.data(), out.dst.data(), /*cb=*/32);
-    CGX_LAUNCH_CHECK();
+    split_row_keys(in1 ? k2.data() : k1.data(), m, out.src.data(), out.dst.data(), s);
   }
   return out;
 }
@@ -2304,21 +2186,6 @@ dbuf<T> xchg_known(louvain_state& S, T const* send, std::vector<size_t> const& c
     if ((int)q != S.comm->rank) n += counts[q];
   S.bytes += n * sizeof(T);
   return exchange_known<T>(*S.comm, send, counts, rcounts, S.s);
-}
-
-// first position of ids >= voff[q] in a sorted u32 array, q = 0..P
-__global__ void k_id_bounds(uint32_t const* ids, int64_t n, int64_t const* voff, int P, int64_t* out)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  int64_t const t = voff[q];
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if ((int64_t)ids[mid] < t) lo = mid + 1;
-    else hi = mid;
-  }
-  out[q] = lo;
 }
 
 // destinations outside this rank's rows [lo, lo + nr) -> their ids, others -> ~0u
@@ -2591,11 +2458,7 @@ int64_t unique_ranks_bitmap(uint32_t const* in, int64_t n, int64_t nv, dbuf<uint
 // per-owner counts of a sorted id list (owner ranges voff, device copy voff_d)
 std::vector<size_t> owner_counts(uint32_t const* ids, int64_t n, dbuf<int64_t> const& voff_d, int P, hipStream_t s)
 {
-  dbuf<int64_t> bnd(P + 1, s);
-  hipLaunchKernelGGL(k_id_bounds, dim3(1), dim3(256), 0, s, ids, n, voff_d.data(), P, bnd.data());
-  CGX_LAUNCH_CHECK();
-  auto c = bounds_to_counts(bnd, P, s);
-  return std::vector<size_t>(c.begin(), c.end());
+  return rank_counts(key_of<uint32_t>{ids}, n, target_voff{voff_d.data(), 0}, P, s);
 }
 
 // collect_values_for_keys: keys (sorted unique ids of this level, n) -> the values
@@ -2867,11 +2730,8 @@ level_graph mg_contract(louvain_state& S, level_graph const& g, mg_level& L, uin
     mw = std::move(cw);
     mk2.resize(std::max<int64_t>(nm, 1), s);  // (scratch for the relabelled keys below)
   } else {
-    dbuf<int64_t> bnd(P + 1, s);
-    hipLaunchKernelGGL(k_key_bounds, dim3(1), dim3(256), 0, s, keys.data(), nce, L.voff_d.data(), P, bnd.data());
-    CGX_LAUNCH_CHECK();
-    auto c64 = bounds_to_counts(bnd, P, s);
-    std::vector<size_t> counts(c64.begin(), c64.end()), rc;
+    auto counts = rank_counts(key_of<u64>{keys.data()}, nce, target_voff{L.voff_d.data(), 32}, P, s);
+    std::vector<size_t> rc;
     auto rk = exchange<u64>(comm, keys.data(), counts, rc, s);
     keys.free();
     auto rw = exchange<double>(comm, cw.data(), counts, rc, s);
@@ -2961,9 +2821,7 @@ level_graph mg_contract(louvain_state& S, level_graph const& g, mg_level& L, uin
       std::swap(mk2, mk);  // sorted keys in mk, weights in out.w
       std::swap(mw, out.w);
     }
-    hipLaunchKernelGGL(k_split_pairs, dim3(blocks(nm)), dim3(kBlock), 0, s, mk.data(), nm, out.src.data(),
-                       out.dst.data(), /*cb=*/32);
-    CGX_LAUNCH_CHECK();
+    split_row_keys(mk.data(), nm, out.src.data(), out.dst.data(), s);
   }
   if (nr) hipLaunchKernelGGL(k_lookup_dense, dim3(blocks(nr)), dim3(kBlock), 0, s, lab_own, nr, dense.data());
   CGX_LAUNCH_CHECK();
@@ -3037,9 +2895,7 @@ void mg_louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolutio
     int64_t const nr = L.nr, r1 = std::max<int64_t>(nr, 1);
     level_voff.push_back(voff);
     dbuf<int64_t> off(nr + 1, s);
-    hipLaunchKernelGGL(k_row_offsets, dim3(blocks(nr + 1)), dim3(kBlock), 0, s, cur.src.data(), cur.ne, nr,
-                       off.data());
-    CGX_LAUNCH_CHECK();
+    lower_bounds(key_of<uint32_t>{cur.src.data()}, cur.ne, target_index{}, nr, off.data(), s);
     dbuf<double> k(r1, s), self(r1, s);
     dbuf<uint8_t> has_edges(r1, s);
     // vertex weights on the global destinations (self loops: dst == row + base), then

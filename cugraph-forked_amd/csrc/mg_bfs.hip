@@ -40,6 +40,7 @@
 #include "capi.hpp"
 #include "comm.hpp"
 #include "mg_graph.hpp"
+#include "mg_route.hpp"
 #include "prims.hpp"
 
 #include <rocprim/device/device_select.hpp>
@@ -50,8 +51,6 @@
 namespace cgx {
 
 namespace {
-
-inline unsigned blocks(int64_t n) { return grid_for(n > 0 ? n : 1, kBlock, 16384); }
 
 constexpr int64_t kPosPad = 16;  // entries past the end of bfs_rows_t::pos
 
@@ -92,81 +91,19 @@ __global__ void k_global_to_pos(uint32_t* ids, int64_t n, int64_t const* voff, i
 }
 
 template <typename V>
-__global__ void k_owner_src(V const* src, int64_t n, int64_t const* voff, int P, int* dest)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dest[i] = mg_owner_of_global((int64_t)src[i], voff, P);
-}
-
-template <typename V>
-__global__ void k_row_keys(V const* src, V const* dst, int64_t n, int64_t base, unsigned long long* keys)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = ((unsigned long long)((int64_t)src[i] - base) << 32) | (unsigned long long)(uint32_t)dst[i];
-}
-
-__global__ void k_split_row_keys(unsigned long long const* keys, int64_t n, uint32_t* row, uint32_t* col)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    row[i] = (uint32_t)(keys[i] >> 32);
-    col[i] = (uint32_t)keys[i];
-  }
-}
-
-__global__ void k_offsets_u32(uint32_t const* row, int64_t ne, int64_t n, int64_t* off)
-{
-  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v <= n; v += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = ne;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)row[mid] < v) lo = mid + 1;
-      else hi = mid;
-    }
-    off[v] = lo;
-  }
-}
-
-template <typename V>
 bfs_rows_t& mg_rows(handle_t& h, graph_t& g)
 {
   mg_graph_t& mg = *g.mg;
   if (mg.bfs_rows) return *static_cast<bfs_rows_t*>(mg.bfs_rows.get());
   hipStream_t s = h.stream;
-  comm_t& comm  = *h.mg->world;
   CGX_EXPECTS(g.num_vertices < (int64_t)UINT32_MAX, CUGRAPH_NOT_IMPLEMENTED, "MG BFS: more than 2^32 vertices");
   auto rows   = std::make_shared<bfs_rows_t>();
   int const P = mg.P;
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  int64_t ne = mg.ne;
   // edges of the 2D block -> owner of the source (a 1D partition by rows)
-  dbuf<int> dest(std::max<int64_t>(ne, 1), s);
-  if (ne)
-    hipLaunchKernelGGL(k_owner_src<V>, dim3(blocks(ne)), dim3(kBlock), 0, s, mg.src.data<V>(), ne, voff_d.data(), P,
-                       dest.data());
-  CGX_LAUNCH_CHECK();
-  dbuf<int> d2(std::max<int64_t>(ne, 1), s);
-  dbuf<int64_t> iv(std::max<int64_t>(ne, 1), s), perm(std::max<int64_t>(ne, 1), s);
-  std::vector<size_t> counts(P, 0);
-  if (ne) {
-    iota<int64_t>(iv.data(), ne, 0, s);
-    radix_sort_pairs<int, int64_t>(dest.data(), d2.data(), iv.data(), perm.data(), ne, 0, bits_for(P), s);
-    auto hd = to_host(d2.data(), ne, s);
-    for (auto q : hd) counts[q]++;
-  }
-  dbuf<V> ps(std::max<int64_t>(ne, 1), s), pd(std::max<int64_t>(ne, 1), s);
-  if (ne) {
-    gather<V, int64_t>(ps.data(), mg.src.data<V>(), perm.data(), ne, s);
-    gather<V, int64_t>(pd.data(), mg.dst.data<V>(), perm.data(), ne, s);
-  }
-  std::vector<size_t> rc;
-  auto rs = exchange<V>(comm, ps.data(), counts, rc, s);
-  auto rd = exchange<V>(comm, pd.data(), counts, rc, s);
-  int64_t m = (int64_t)rs.n;
+  auto e          = edges_to_source_owner<V, float>(h, g, /*want_weights=*/false);
+  int64_t const m = e.n, m1 = std::max<int64_t>(m, 1);
   rows->n_own = mg.n_own();
   rows->ne    = m;
-  dbuf<unsigned long long> k1(std::max<int64_t>(m, 1), s), k2(std::max<int64_t>(m, 1), s);
-  dbuf<uint32_t> rr(std::max<int64_t>(m, 1), s);
   int64_t maxn = 0;
   for (int q = 0; q < P; ++q) maxn = std::max(maxn, mg.voff[q + 1] - mg.voff[q]);
   rows->words = std::max<int64_t>((maxn + 31) / 32, 1);
@@ -177,21 +114,20 @@ bfs_rows_t& mg_rows(handle_t& h, graph_t& g)
   HIP_CHECK(hipMemsetAsync(rows->pos.data<uint32_t>() + m, 0, kPosPad * sizeof(uint32_t), s));
   rows->off.set_stream(s);
   rows->off.resize((rows->n_own + 1) * sizeof(int64_t));
+  dbuf<uint32_t> rr(m1, s);
   if (m) {
-    hipLaunchKernelGGL(k_row_keys<V>, dim3(blocks(m)), dim3(kBlock), 0, s, rs.data(), rd.data(), m, mg.voff[mg.p],
-                       k1.data());
-    CGX_LAUNCH_CHECK();
+    dbuf<unsigned long long> k1(m, s), k2(m, s);
+    row_keys<V>(e.src.data(), e.dst.data(), m, mg.voff[mg.p], k1.data(), s);
+    e.src.free();
+    e.dst.free();
     radix_sort_keys<unsigned long long>(k1.data(), k2.data(), m, 0, 64, s);
-    hipLaunchKernelGGL(k_split_row_keys, dim3(blocks(m)), dim3(kBlock), 0, s, k2.data(), m, rr.data(),
-                       rows->pos.data<uint32_t>());
-    CGX_LAUNCH_CHECK();
+    split_row_keys(k2.data(), m, rr.data(), rows->pos.data<uint32_t>(), s);
+    auto voff_d = device_voff(mg, s);
     hipLaunchKernelGGL(k_global_to_pos, dim3(blocks(m)), dim3(kBlock), 0, s, rows->pos.data<uint32_t>(), m,
                        voff_d.data(), P, rows->words * 32);
     CGX_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_offsets_u32, dim3(blocks(rows->n_own + 1)), dim3(kBlock), 0, s, rr.data(), m, rows->n_own,
-                     rows->off.data<int64_t>());
-  CGX_LAUNCH_CHECK();
+  lower_bounds(key_of<uint32_t>{rr.data()}, m, target_index{}, rows->n_own, rows->off.data<int64_t>(), s);
   HIP_CHECK(hipStreamSynchronize(s));
   mg.bfs_rows = rows;
   return *rows;
@@ -203,13 +139,6 @@ struct bfs_block_t {
   buffer off;  // int64[nrow + 1]
   buffer idx;  // uint32 global destination ids, ascending per row
 };
-
-template <typename V>
-__global__ void k_block_keys(V const* src, V const* dst, int64_t n, int64_t row_lo, unsigned long long* keys)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = ((unsigned long long)((int64_t)src[i] - row_lo) << 32) | (unsigned long long)(uint32_t)dst[i];
-}
 
 template <typename V>
 bfs_block_t& mg_block_csr(handle_t& h, graph_t& g)
@@ -230,17 +159,11 @@ bfs_block_t& mg_block_csr(handle_t& h, graph_t& g)
   blk->off.set_stream(s);
   blk->off.resize((blk->nrow + 1) * sizeof(int64_t));
   if (m) {
-    hipLaunchKernelGGL(k_block_keys<V>, dim3(blocks(m)), dim3(kBlock), 0, s, mg.src.data<V>(), mg.dst.data<V>(), m,
-                       blk->row_lo, k1.data());
-    CGX_LAUNCH_CHECK();
+    row_keys<V>(mg.src.data<V>(), mg.dst.data<V>(), m, blk->row_lo, k1.data(), s);
     radix_sort_keys<unsigned long long>(k1.data(), k2.data(), m, 0, 64, s);
-    hipLaunchKernelGGL(k_split_row_keys, dim3(blocks(m)), dim3(kBlock), 0, s, k2.data(), m, rr.data(),
-                       blk->idx.data<uint32_t>());
-    CGX_LAUNCH_CHECK();
+    split_row_keys(k2.data(), m, rr.data(), blk->idx.data<uint32_t>(), s);
   }
-  hipLaunchKernelGGL(k_offsets_u32, dim3(blocks(blk->nrow + 1)), dim3(kBlock), 0, s, rr.data(), m, blk->nrow,
-                     blk->off.data<int64_t>());
-  CGX_LAUNCH_CHECK();
+  lower_bounds(key_of<uint32_t>{rr.data()}, m, target_index{}, blk->nrow, blk->off.data<int64_t>(), s);
   HIP_CHECK(hipStreamSynchronize(s));
   mg.bfs_block = blk;
   return *blk;
@@ -886,8 +809,7 @@ void mg_bfs_impl(handle_t& h, graph_t& g, array_view_t* sources, bool dir_opt, s
                      dist, qa.data(), ctr.data(), flag.data(), rows.off.data<int64_t>());
   CGX_LAUNCH_CHECK();
 
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(mg, s);
   // own frontier bitmap segments (current / next: the probe writes every word of the
   // next, so neither needs a memset per level once cleared here) and the allgathered bitmap
   dbuf<uint32_t> seg(rows.words, s), seg_next(rows.words, s), bitmap(rows.words * P, s);

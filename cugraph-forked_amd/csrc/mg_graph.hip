@@ -3,6 +3,7 @@
 // (reference cpp/src/c_api/graph_mg.cpp:138-259).
 #include "mg_graph.hpp"
 
+#include "mg_route.hpp"
 #include "prims.hpp"
 
 #include <rocprim/device/device_run_length_encode.hpp>
@@ -19,8 +20,6 @@ int mg_graph_t::owner_of_global(int64_t x) const
 }
 
 namespace {
-
-inline unsigned blocks(int64_t n) { return grid_for(n > 0 ? n : 1, kBlock, 16384); }
 
 template <typename T>
 __device__ int64_t lower_bound_dev(T const* a, int64_t n, T x)
@@ -72,85 +71,6 @@ __global__ void k_owner_ext(V const* x, size_t n, int P, int* dest)
 {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     dest[i] = mg_owner_of_ext((int64_t)x[i], P);
-}
-
-template <typename V>
-__global__ void k_owner_global(V const* x, size_t n, int64_t const* voff, int P, int self, int* dest)
-{
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    int64_t v = (int64_t)x[i];
-    dest[i]   = (v >= 0 && v < voff[P]) ? mg_owner_of_global(v, voff, P) : self;
-  }
-}
-
-// per-rank counts of a destination-sorted array: two binary searches per rank (a
-// per-element atomicAdd onto the P counters serialised at the memory side: 14 ms for
-// 2.4M elements on one rank, RMAT-22's predecessor routing in the MG BFS)
-__global__ void k_rank_counts(int const* dest_sorted, int64_t n, int P, int64_t* cnt)
-{
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < P; q += gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = n;  // first position with dest >= q
-    while (lo < hi) {
-      int64_t const mid = (lo + hi) >> 1;
-      if (dest_sorted[mid] < q) lo = mid + 1;
-      else hi = mid;
-    }
-    int64_t a = lo, b = n;  // first position with dest >= q + 1
-    while (a < b) {
-      int64_t const mid = (a + b) >> 1;
-      if (dest_sorted[mid] < q + 1) a = mid + 1;
-      else b = mid;
-    }
-    cnt[q] = a - lo;
-  }
-}
-
-template <typename T, typename I>
-__global__ void k_gather_by(T const* in, I const* idx, size_t n, T* out)
-{
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = in[idx[i]];
-}
-
-template <typename T, typename I>
-__global__ void k_scatter_by(T const* in, I const* idx, size_t n, T* out)
-{
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[idx[i]] = in[i];
-}
-
-// Order positions [0, n) by destination rank; per-rank counts on the host.
-struct routing {
-  dbuf<int64_t> perm;  // sorted position -> original position
-  std::vector<size_t> counts;
-};
-
-routing route_by(int const* dest, size_t n, int P, hipStream_t s)
-{
-  routing rt;
-  rt.perm.resize(std::max<size_t>(n, 1), s);
-  rt.counts.assign(P, 0);
-  if (!n) return rt;
-  dbuf<int> d2(n, s);
-  dbuf<int64_t> iv(n, s);
-  iota<int64_t>(iv.data(), n, 0, s);
-  radix_sort_pairs<int, int64_t>(dest, d2.data(), iv.data(), rt.perm.data(), n, 0, bits_for(P), s);
-  dbuf<int64_t> cnt(P, s);
-  hipLaunchKernelGGL(k_rank_counts, dim3(1), dim3(64), 0, s, d2.data(), (int64_t)n, P, cnt.data());
-  CGX_LAUNCH_CHECK();
-  auto h = to_host(cnt.data(), P, s);
-  for (int q = 0; q < P; ++q) rt.counts[q] = (size_t)h[q];
-  return rt;
-}
-
-template <typename T>
-dbuf<T> permute(T const* in, dbuf<int64_t> const& perm, size_t n, hipStream_t s)
-{
-  dbuf<T> out(std::max<size_t>(n, 1), s);
-  if (n)
-    hipLaunchKernelGGL((k_gather_by<T, int64_t>), dim3(blocks(n)), dim3(kBlock), 0, s, in, perm.data(), n, out.data());
-  CGX_LAUNCH_CHECK();
-  return out;
 }
 
 // ---------------------------------------------------------------- build kernels
@@ -228,20 +148,15 @@ __global__ void k_count_neg(V const* x, size_t n, int* bad)
 // Route `q` (n keys) to `dest` ranks, have the owner compute `answer(recv, m, out)`,
 // return the answers in the original order (into `out`).
 template <typename V, typename F>
-void route_query(comm_t& comm, V const* q, int const* dest, size_t n, V* out, F&& answer, hipStream_t s)
+void route_query(comm_t& comm, V const* q, int* dest, size_t n, V* out, F&& answer, hipStream_t s)
 {
-  int P   = comm.size;
-  auto rt = route_by(dest, n, P, s);
-  auto qs = permute<V>(q, rt.perm, n, s);
+  auto rt = route_by(dest, n, comm.size, s);
   std::vector<size_t> rc, back_rc;
-  auto got = exchange<V>(comm, qs.data(), rt.counts, rc, s);
+  auto got = route_column<V>(comm, rt, q, rc, s);
   dbuf<V> ans(std::max<size_t>(got.n, 1), s);
   if (got.n) answer(got.data(), got.n, ans.data());
   auto back = exchange<V>(comm, ans.data(), rc, back_rc, s);
-  if (n)
-    hipLaunchKernelGGL((k_scatter_by<V, int64_t>), dim3(blocks(n)), dim3(kBlock), 0, s, back.data(), rt.perm.data(), n,
-                       out);
-  CGX_LAUNCH_CHECK();
+  scatter<V, int64_t>(out, back.data(), rt.perm.data(), n, s);
 }
 
 template <typename V, typename R>
@@ -307,12 +222,9 @@ void build_mg_impl(handle_t& h, graph_t& g, array_view_t const& srcv, array_view
     dbuf<int> md(std::max<size_t>(nm, 1), s);
     if (nm) hipLaunchKernelGGL(k_owner_ext<V>, dim3(blocks(nm)), dim3(kBlock), 0, s, mu.data(), nm, P, md.data());
     CGX_LAUNCH_CHECK();
-    auto rt  = route_by(md.data(), nm, P, s);
-    auto mus = permute<V>(mu.data(), rt.perm, nm, s);
-    auto mcs = permute<int64_t>(mc.data(), rt.perm, nm, s);
-    std::vector<size_t> rc1, rc2;
-    auto rid = exchange<V>(comm, mus.data(), rt.counts, rc1, s);
-    auto rcn = exchange<int64_t>(comm, mcs.data(), rt.counts, rc2, s);
+    auto rt = route_by(md.data(), nm, P, s);
+    std::vector<size_t> rc;
+    auto [rid, rcn] = route_columns(comm, rt, rc, s, mu.data(), mc.data());
     if (rid.n)
       hipLaunchKernelGGL(k_add_degrees<V>, dim3(blocks(rid.n)), dim3(kBlock), 0, s, rid.data(), rcn.data(), rid.n,
                          O.data(), nO, deg.data());
@@ -365,8 +277,7 @@ void build_mg_impl(handle_t& h, graph_t& g, array_view_t const& srcv, array_view
   CGX_LAUNCH_CHECK();
 
   // 8. edges to their 2D block
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg->voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(*mg, s);
   dbuf<int> ed(std::max<size_t>(n, 1), s);
   if (n)
     hipLaunchKernelGGL(k_edge_target<V>, dim3(blocks(n)), dim3(kBlock), 0, s, s2.data(), d2.data(), n,
@@ -374,22 +285,11 @@ void build_mg_impl(handle_t& h, graph_t& g, array_view_t const& srcv, array_view
   CGX_LAUNCH_CHECK();
   auto rtE = route_by(ed.data(), n, P, s);
   std::vector<size_t> rce;
-  {
-    auto ps = permute<V>(s2.data(), rtE.perm, n, s);
-    auto rs = exchange<V>(comm, ps.data(), rtE.counts, rce, s);
-    mg->ne  = (int64_t)rs.n;
-    mg->src = std::move(rs.b);
-  }
-  {
-    auto pd = permute<V>(d2.data(), rtE.perm, n, s);
-    auto rd = exchange<V>(comm, pd.data(), rtE.counts, rce, s);
-    mg->dst = std::move(rd.b);
-  }
-  if (wv) {
-    auto pw = permute<R>(wv->as<R>(), rtE.perm, n, s);
-    auto rw = exchange<R>(comm, pw.data(), rtE.counts, rce, s);
-    mg->w   = std::move(rw.b);
-  }
+  auto rs = route_column<V>(comm, rtE, s2.data(), rce, s);
+  mg->ne  = (int64_t)rs.n;
+  mg->src = std::move(rs.b);
+  mg->dst = route_column<V>(comm, rtE, d2.data(), rce, s).b;
+  if (wv) mg->w = route_column<R>(comm, rtE, wv->as<R>(), rce, s).b;
   HIP_CHECK(hipStreamSynchronize(s));
   g.num_vertices = V_total;
   g.num_edges    = comm.host_allreduce<int64_t>((int64_t)n, CGX_COMM_SUM, s);
@@ -445,16 +345,12 @@ void mg_global_to_ext(handle_t& h, graph_t& g, void* ids, size_t n)
   hipStream_t s = h.stream;
   comm_t& comm  = *h.mg->world;
   mg_graph_t& mg = *g.mg;
-  dbuf<int64_t> voff_d(mg.P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (mg.P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(mg, s);
   auto run = [&](auto tag) {
     using V = decltype(tag);
     V* x    = static_cast<V*>(ids);
     dbuf<int> dest(std::max<size_t>(n, 1), s);
-    if (n)
-      hipLaunchKernelGGL(k_owner_global<V>, dim3(blocks(n)), dim3(kBlock), 0, s, x, n, voff_d.data(), mg.P, mg.p,
-                         dest.data());
-    CGX_LAUNCH_CHECK();
+    owners_of_global<V>(x, (int64_t)n, voff_d.data(), mg.P, dest.data(), s, /*self=*/mg.p);
     int64_t lo = mg.voff[mg.p], hi = mg.voff[mg.p + 1];
     route_query<V>(
       comm, x, dest.data(), n, x,
@@ -504,8 +400,7 @@ void ensure_rep_impl(handle_t& h, graph_t& g)
   if (mg.n_own())
     HIP_CHECK(hipMemcpyAsync(pad.data(), g.number_map.data(), mg.n_own() * sizeof(V), hipMemcpyDeviceToDevice, s));
   comm.allgather<V>(pad.data(), gath.data(), (size_t)mx, s);
-  dbuf<int64_t> voff_d(mg.P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (mg.P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(mg, s);
   for (buffer* b : {&mg.rep_nmap, &mg.rep_ext_sorted, &mg.rep_gid}) {
     b->set_stream(s);
     b->resize(std::max<int64_t>(Vt, 1) * sizeof(V));

@@ -14,6 +14,11 @@
 //    column c the destinations of ranks c, C+c, 2C+c, ...  A PageRank iteration
 //    then needs an allgather of x~ inside the row and a reduce-scatter of partial
 //    sums inside the column.
+//  * Algorithms that want the out-edges of their own vertices instead (bottom-up BFS,
+//    SSSP, Louvain) get that 1D partition by source owner from the 2D block through
+//    mg_route.hpp, which holds every "send it to its owner" step of the MG path: owner
+//    of a global id, per-rank bounds of sorted arrays, route_by / route_columns,
+//    edges_to_source_owner, the row sort keys.
 #pragma once
 
 #include "capi.hpp"
@@ -34,9 +39,11 @@ struct mg_graph_t {
   // this rank's 2D block of edges (global ids), weights optional
   int64_t ne = 0;
   buffer src, dst, w;
-  // per-algorithm caches (pagerank.hip, mg_bfs.hip, mg_sssp.hip)
-  std::shared_ptr<void> pr_block;
-  std::shared_ptr<void> bfs_rows;
+  // per-algorithm caches, built on first use.  bfs_rows and sssp_rows are the algorithm's
+  // own form of mg_route.hpp's edges_to_source_owner rows (Louvain rebuilds its level 0
+  // from the same call every time and caches nothing)
+  std::shared_ptr<void> pr_block;   // the 2D block's push structures (pagerank.hip)
+  std::shared_ptr<void> bfs_rows;   // out-rows by source owner as frontier-bitmap positions (mg_bfs.hip)
   std::shared_ptr<void> bfs_block;  // the 2D block as a CSR over the row's sources (mg_bfs.hip)
   std::shared_ptr<void> sssp_rows;  // weighted out-rows by source owner (mg_sssp.hip)
   // every vertex's external id on every rank (global -> external, and external ids

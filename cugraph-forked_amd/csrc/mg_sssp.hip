@@ -27,6 +27,7 @@
 #include "capi.hpp"
 #include "comm.hpp"
 #include "mg_graph.hpp"
+#include "mg_route.hpp"
 #include "prims.hpp"
 
 #include <rocprim/device/device_reduce_by_key.hpp>
@@ -37,8 +38,6 @@
 namespace cgx {
 
 namespace {
-
-inline unsigned blocks(int64_t n) { return grid_for(n > 0 ? n : 1, kBlock, 16384); }
 
 template <typename W>
 struct wrows_t {
@@ -67,78 +66,6 @@ __device__ __forceinline__ W atomic_min_nonneg(W* p, W x)
   return *reinterpret_cast<W*>(&old);
 }
 
-template <typename V>
-__global__ void k_src_owner(V const* src, int64_t n, int64_t const* voff, int P, int* dest)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dest[i] = mg_owner_of_global((int64_t)src[i], voff, P);
-}
-
-// first position of value q in a sorted int array, q = 0..P
-__global__ void k_int_bounds(int const* sorted, int64_t n, int P, int64_t* out)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (sorted[mid] < q) lo = mid + 1;
-    else hi = mid;
-  }
-  out[q] = lo;
-}
-
-// first position of keys >= voff[q] (q < P) / of the UINT32_MAX sentinel run (q = P)
-__global__ void k_u32_bounds(uint32_t const* keys, int64_t n, int64_t const* voff, int P, int64_t* out)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  unsigned long long const t = (unsigned long long)voff[q];
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if ((unsigned long long)keys[mid] < t) lo = mid + 1;
-    else hi = mid;
-  }
-  out[q] = lo;
-}
-
-template <typename V>
-__global__ void k_row_keys(V const* src, V const* dst, int64_t n, int64_t base, unsigned long long* keys)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = ((unsigned long long)((int64_t)src[i] - base) << 32) | (unsigned long long)(uint32_t)dst[i];
-}
-
-__global__ void k_split_keys(unsigned long long const* keys, int64_t n, uint32_t* row, uint32_t* col)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    row[i] = (uint32_t)(keys[i] >> 32);
-    col[i] = (uint32_t)keys[i];
-  }
-}
-
-__global__ void k_row_offsets(uint32_t const* row, int64_t ne, int64_t n, int64_t* off)
-{
-  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v <= n; v += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = ne;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if ((int64_t)row[mid] < v) lo = mid + 1;
-      else hi = mid;
-    }
-    off[v] = lo;
-  }
-}
-
-std::vector<size_t> bounds_counts(dbuf<int64_t> const& b, int P, hipStream_t s)
-{
-  auto hb = to_host(b.data(), P + 1, s);
-  std::vector<size_t> c(P);
-  for (int q = 0; q < P; ++q) c[q] = (size_t)(hb[q + 1] - hb[q]);
-  return c;
-}
-
 // the 2D block's weighted edges -> out-rows of this rank's vertices (cached)
 template <typename V, typename W>
 wrows_t<W>& mg_wrows(handle_t& h, graph_t& g)
@@ -146,34 +73,9 @@ wrows_t<W>& mg_wrows(handle_t& h, graph_t& g)
   mg_graph_t& mg = *g.mg;
   if (mg.sssp_rows) return *static_cast<wrows_t<W>*>(mg.sssp_rows.get());
   hipStream_t s = h.stream;
-  comm_t& comm  = *h.mg->world;
-  int const P   = mg.P;
   auto rows     = std::make_shared<wrows_t<W>>();
-  dbuf<int64_t> voff_d(P + 1, s), bnd(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  int64_t const ne = mg.ne, n1 = std::max<int64_t>(ne, 1);
-  dbuf<int> dest(n1, s), d2(n1, s);
-  dbuf<int64_t> iv(n1, s), perm(n1, s);
-  dbuf<V> ps(n1, s), pd(n1, s);
-  dbuf<W> pw(n1, s);
-  if (ne) {
-    hipLaunchKernelGGL(k_src_owner<V>, dim3(blocks(ne)), dim3(kBlock), 0, s, mg.src.data<V>(), ne, voff_d.data(), P,
-                       dest.data());
-    CGX_LAUNCH_CHECK();
-    iota<int64_t>(iv.data(), ne, 0, s);
-    radix_sort_pairs<int, int64_t>(dest.data(), d2.data(), iv.data(), perm.data(), ne, 0, bits_for(P), s);
-    gather<V, int64_t>(ps.data(), mg.src.data<V>(), perm.data(), ne, s);
-    gather<V, int64_t>(pd.data(), mg.dst.data<V>(), perm.data(), ne, s);
-    gather<W, int64_t>(pw.data(), mg.w.data<W>(), perm.data(), ne, s);
-  }
-  hipLaunchKernelGGL(k_int_bounds, dim3(1), dim3(256), 0, s, d2.data(), ne, P, bnd.data());
-  CGX_LAUNCH_CHECK();
-  auto counts = bounds_counts(bnd, P, s);
-  std::vector<size_t> rc;
-  auto rs = exchange<V>(comm, ps.data(), counts, rc, s);
-  auto rd = exchange<V>(comm, pd.data(), counts, rc, s);
-  auto rw = exchange<W>(comm, pw.data(), counts, rc, s);
-  int64_t const m = (int64_t)rs.n, m1 = std::max<int64_t>(m, 1);
+  auto e        = edges_to_source_owner<V, W>(h, g, /*want_weights=*/true);
+  int64_t const m = e.n, m1 = std::max<int64_t>(m, 1);
   rows->n_own = mg.n_own();
   rows->ne    = m;
   rows->off.resize(rows->n_own + 1, s);
@@ -182,16 +84,13 @@ wrows_t<W>& mg_wrows(handle_t& h, graph_t& g)
   dbuf<uint32_t> rr(m1, s);
   if (m) {
     dbuf<unsigned long long> k1(m, s), k2(m, s);
-    hipLaunchKernelGGL(k_row_keys<V>, dim3(blocks(m)), dim3(kBlock), 0, s, rs.data(), rd.data(), m, mg.voff[mg.p],
-                       k1.data());
-    CGX_LAUNCH_CHECK();
-    radix_sort_pairs<unsigned long long, W>(k1.data(), k2.data(), rw.data(), rows->w.data(), (size_t)m, 0, 64, s);
-    hipLaunchKernelGGL(k_split_keys, dim3(blocks(m)), dim3(kBlock), 0, s, k2.data(), m, rr.data(), rows->idx.data());
-    CGX_LAUNCH_CHECK();
+    row_keys<V>(e.src.data(), e.dst.data(), m, mg.voff[mg.p], k1.data(), s);
+    e.src.free();
+    e.dst.free();
+    radix_sort_pairs<unsigned long long, W>(k1.data(), k2.data(), e.w.data(), rows->w.data(), (size_t)m, 0, 64, s);
+    split_row_keys(k2.data(), m, rr.data(), rows->idx.data(), s);
   }
-  hipLaunchKernelGGL(k_row_offsets, dim3(blocks(rows->n_own + 1)), dim3(kBlock), 0, s, rr.data(), m, rows->n_own,
-                     rows->off.data());
-  CGX_LAUNCH_CHECK();
+  lower_bounds(key_of<uint32_t>{rr.data()}, m, target_index{}, rows->n_own, rows->off.data(), s);
   HIP_CHECK(hipStreamSynchronize(s));
   mg.sssp_rows = rows;
   return *rows;
@@ -325,21 +224,6 @@ struct same_hi {
   __host__ __device__ bool operator()(unsigned long long a, unsigned long long b) const { return (a >> 32) == (b >> 32); }
 };
 
-// first position with key >= voff[q] << 32 (q < P) / of the ~0 sentinel run (q = P)
-__global__ void k_key_split(unsigned long long const* keys, int64_t n, int64_t const* voff, int P, int64_t* pos)
-{
-  int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  unsigned long long bound = (unsigned long long)voff[q] << 32;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < bound) lo = mid + 1;
-    else hi = mid;
-  }
-  pos[q] = lo;
-}
-
 template <typename V>
 __global__ void k_set_pred(unsigned long long const* keys, int64_t n, int64_t lo, V* pred)
 {
@@ -423,8 +307,7 @@ void mg_sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool wa
   double const ne_g = (double)g.num_edges;
   W const delta     = ne_g > 0 ? (W)std::max(64.0 * (wsum / ne_g) / (ne_g / (double)g.num_vertices), 1e-30) : W(1);
 
-  dbuf<int64_t> voff_d(P + 1, s), pos(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(mg, s);
   dbuf<int> stamp(n1, s);
   fill<int>(stamp.data(), n1, -1, s);
   dbuf<W> relaxed(n1, s);  // the distance each vertex last pushed (BIG: never)
@@ -501,11 +384,7 @@ void mg_sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool wa
     }
     // 2. to the owners (the sentinel run sorts last and is not sent)
     std::vector<size_t> counts(P, 0);
-    if (nu) {
-      hipLaunchKernelGGL(k_u32_bounds, dim3(1), dim3(256), 0, s, uk.data(), nu, voff_d.data(), P, pos.data());
-      CGX_LAUNCH_CHECK();
-      counts = bounds_counts(pos, P, s);
-    }
+    if (nu) counts = rank_counts(key_of<uint32_t>{uk.data()}, nu, target_voff{voff_d.data(), 0}, P, s);
     std::vector<size_t> rc;
     auto rk = exchange<uint32_t>(comm, uk.data(), counts, rc, s);
     auto rv = exchange<W>(comm, uv.data(), counts, rc, s);
@@ -561,11 +440,7 @@ void mg_sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool wa
       nt = (int64_t)to_host_scalar(c1.data(), s);
     }
     std::vector<size_t> counts(P, 0);
-    if (nt) {
-      hipLaunchKernelGGL(k_key_split, dim3(1), dim3(256), 0, s, tu.data(), nt, voff_d.data(), P, pos.data());
-      CGX_LAUNCH_CHECK();
-      counts = bounds_counts(pos, P, s);
-    }
+    if (nt) counts = rank_counts(key_of<unsigned long long>{tu.data()}, nt, target_voff{voff_d.data(), 32}, P, s);
     std::vector<size_t> rc;
     auto got = exchange<int64_t>(comm, reinterpret_cast<int64_t const*>(tu.data()), counts, rc, s);
     if (got.n)

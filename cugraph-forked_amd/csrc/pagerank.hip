@@ -29,6 +29,7 @@
 #include "capi.hpp"
 #include "comm.hpp"
 #include "mg_graph.hpp"
+#include "mg_route.hpp"
 #include "prims.hpp"
 #include "schedule.hpp"
 
@@ -3225,20 +3226,6 @@ struct mg_pr_block {
   }
 };
 
-// first position of each key 0..K in a sorted array (K + 1 binary searches)
-__global__ void k_sorted_starts(uint32_t const* sorted, int64_t n, int K, int64_t* st)
-{
-  for (int k = threadIdx.x; k <= K; k += blockDim.x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      int64_t const mid = (lo + hi) >> 1;
-      if ((int)sorted[mid] < k) lo = mid + 1;
-      else hi = mid;
-    }
-    st[k] = lo;
-  }
-}
-
 // chunk of each edge's destination row, and the row within the chunk's [owner][row] array
 __global__ void k_mg_row_chunks(uint32_t* rows, int64_t ne, int64_t nmax_col, int64_t cs, uint32_t* chunk)
 {
@@ -3309,8 +3296,7 @@ mg_pr_block& mg_block(handle_t& h, graph_t& g)
   for (int q = 0; q < C; ++q) blk->nmax_row = std::max(blk->nmax_row, mg.voff[r * C + q + 1] - mg.voff[r * C + q]);
   for (int q = 0; q < R_; ++q) blk->nmax_col = std::max(blk->nmax_col, mg.voff[q * C + c + 1] - mg.voff[q * C + c]);
   int64_t const ne = mg.ne, n_cols = C * blk->nmax_row, n_rows = R_ * blk->nmax_col;
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto voff_d = device_voff(mg, s);
   dbuf<uint32_t> rows(std::max<int64_t>(ne, 1), s), cols(std::max<int64_t>(ne, 1), s);
   if (ne)
     hipLaunchKernelGGL(k_mg_block_coo<V>, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, mg.src.data<V>(),
@@ -3351,8 +3337,7 @@ mg_pr_block& mg_block(handle_t& h, graph_t& g)
     gather<uint32_t, uint32_t>(cols_s.data(), cols.data(), perm.data(), ne, s);
     if (w_in) gather<R, uint32_t>(w_s.data(), w_in, perm.data(), ne, s);
     dbuf<int64_t> st_d(K + 1, s);
-    hipLaunchKernelGGL(k_sorted_starts, dim3(1), dim3(64), 0, s, chunk_s.data(), ne, K, st_d.data());
-    CGX_LAUNCH_CHECK();
+    lower_bounds(key_of<uint32_t>{chunk_s.data()}, ne, target_index{}, K, st_d.data(), s);  // chunk k's first edge
     auto const st = to_host(st_d.data(), K + 1, s);
     for (int k = 0; k < K; ++k)
       build_push_from_coo<uint32_t, R>(s, rows_s.data() + st[k], cols_s.data() + st[k],
@@ -3414,13 +3399,6 @@ mg_pr_block& mg_block(handle_t& h, graph_t& g)
   return *blk;
 }
 
-template <typename V>
-__global__ void k_pr_owner(V const* gid, int64_t n, int64_t const* voff, int P, int* dest)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dest[i] = mg_owner_of_global((int64_t)gid[i], voff, P);
-}
-
 template <typename V, typename R>
 __global__ void k_scatter_owned(V const* gid, R const* val, int64_t n, int64_t lo, double scale, R* owned)
 {
@@ -3477,25 +3455,12 @@ mg_pairs_info mg_pairs_to_owned(handle_t& h, graph_t& g, array_view_t const* vv,
   info.negatives = comm.host_allreduce<int64_t>(lneg, CGX_COMM_SUM, s);
   double const scale = scale_of(info);
   // to the owners: sort by owner, exchange, scatter
-  dbuf<int64_t> voff_d(P + 1, s);
-  HIP_CHECK(hipMemcpyAsync(voff_d.data(), mg.voff.data(), (P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  dbuf<int> dest(std::max<size_t>(n, 1), s), d2(std::max<size_t>(n, 1), s);
-  dbuf<int64_t> iv(std::max<size_t>(n, 1), s), perm(std::max<size_t>(n, 1), s);
-  dbuf<V> sid(std::max<size_t>(n, 1), s);
-  dbuf<R> sval(std::max<size_t>(n, 1), s);
-  std::vector<size_t> counts(P, 0), rc;
-  if (n) {
-    hipLaunchKernelGGL(k_pr_owner<V>, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, ids.data(), (int64_t)n,
-                       voff_d.data(), P, dest.data());
-    CGX_LAUNCH_CHECK();
-    iota<int64_t>(iv.data(), n, 0, s);
-    radix_sort_pairs<int, int64_t>(dest.data(), d2.data(), iv.data(), perm.data(), n, 0, bits_for(P), s);
-    gather<V, int64_t>(sid.data(), ids.data(), perm.data(), n, s);
-    gather<R, int64_t>(sval.data(), vals.data(), perm.data(), n, s);
-    for (int q : to_host(d2.data(), n, s)) counts[q]++;
-  }
-  auto rid  = exchange<V>(comm, sid.data(), counts, rc, s);
-  auto rval = exchange<R>(comm, sval.data(), counts, rc, s);
+  auto voff_d = device_voff(mg, s);
+  dbuf<int> dest(std::max<size_t>(n, 1), s);
+  owners_of_global<V>(ids.data(), (int64_t)n, voff_d.data(), P, dest.data(), s);
+  auto rt = route_by(dest.data(), n, P, s);
+  std::vector<size_t> rc;
+  auto [rid, rval] = route_columns(comm, rt, rc, s, ids.data(), vals.data());
   if (rid.n)
     hipLaunchKernelGGL((k_scatter_owned<V, R>), dim3(grid_for(rid.n, kBlock, 4096)), dim3(kBlock), 0, s, rid.data(),
                        rval.data(), (int64_t)rid.n, lo, scale, owned);
