@@ -122,6 +122,11 @@ class buffer {
       }
     }
   }
+  void resize(size_t bytes, hipStream_t s)
+  {
+    stream_ = s;
+    resize(bytes);
+  }
   void set_stream(hipStream_t s) { stream_ = s; }
   // Frees are stream-ordered on the allocating stream.  Handle streams come from a
   // process-wide pool and are never destroyed (capi_core.cpp), so a buffer may

@@ -1540,40 +1540,48 @@ __device__ __forceinline__ int64_t row_of_edge(E const* off, int64_t lo, int64_t
   return lo;
 }
 
+// one tile [e0, e1) of at most kRowsTile edges, by the whole block: f(e, row, the row's
+// first edge) for every edge of it.  s_r[2] and s_off[kRowsTile + 1] are the caller's LDS.
+template <typename E, typename F>
+__device__ __forceinline__ void tile_edge_rows(E const* off, int64_t nv, int64_t e0, int64_t e1, int64_t* s_r,
+                                               E* s_off, F f)
+{
+  if (threadIdx.x == 0) {
+    s_r[0] = row_of_edge(off, 0, nv - 1, e0);
+    s_r[1] = row_of_edge(off, s_r[0], nv - 1, e1 - 1);
+  }
+  __syncthreads();
+  int64_t const r0 = s_r[0], r1 = s_r[1];
+  bool const staged = r1 - r0 < kRowsTile;
+  if (staged)
+    for (int64_t i = threadIdx.x; i <= r1 - r0; i += blockDim.x) s_off[i] = off[r0 + i];
+  __syncthreads();
+  for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
+    int64_t r;
+    if (staged) {
+      int64_t lo = 0, hi = r1 - r0;
+      while (lo < hi) {
+        int64_t const mid = (lo + hi + 1) >> 1;
+        if ((int64_t)s_off[mid] <= e) lo = mid;
+        else hi = mid - 1;
+      }
+      r = r0 + lo;
+    } else {
+      r = row_of_edge(off, r0, r1, e);
+    }
+    f(e, r, (int64_t)(staged ? s_off[r - r0] : off[r]));
+  }
+  __syncthreads();
+}
+
 template <typename E>
 __global__ __launch_bounds__(256) void k_edge_rows(E const* off, int64_t nv, int64_t ne, uint32_t* rows)
 {
   __shared__ int64_t s_r[2];
   __shared__ E s_off[kRowsTile + 1];
-  for (int64_t e0 = (int64_t)blockIdx.x * kRowsTile; e0 < ne; e0 += (int64_t)gridDim.x * kRowsTile) {
-    int64_t const e1 = min(e0 + kRowsTile, ne);
-    if (threadIdx.x == 0) {
-      s_r[0] = row_of_edge(off, 0, nv - 1, e0);
-      s_r[1] = row_of_edge(off, s_r[0], nv - 1, e1 - 1);
-    }
-    __syncthreads();
-    int64_t const r0 = s_r[0], r1 = s_r[1];
-    bool const staged = r1 - r0 < kRowsTile;
-    if (staged)
-      for (int64_t i = threadIdx.x; i <= r1 - r0; i += blockDim.x) s_off[i] = off[r0 + i];
-    __syncthreads();
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-      int64_t r;
-      if (staged) {
-        int64_t lo = 0, hi = r1 - r0;
-        while (lo < hi) {
-          int64_t const mid = (lo + hi + 1) >> 1;
-          if ((int64_t)s_off[mid] <= e) lo = mid;
-          else hi = mid - 1;
-        }
-        r = r0 + lo;
-      } else {
-        r = row_of_edge(off, r0, r1, e);
-      }
-      rows[e] = (uint32_t)r;
-    }
-    __syncthreads();
-  }
+  for (int64_t e0 = (int64_t)blockIdx.x * kRowsTile; e0 < ne; e0 += (int64_t)gridDim.x * kRowsTile)
+    tile_edge_rows(off, nv, e0, min(e0 + kRowsTile, ne), s_r, s_off,
+                   [&](int64_t e, int64_t r, int64_t) { rows[e] = (uint32_t)r; });
 }
 
 // key = window << 32 | source, value = edge position; with source bands (cut > 0) the
@@ -1596,16 +1604,21 @@ __global__ void k_push_keys(C const* cols, uint32_t const* rows, int64_t ne, int
 // keys come out of the out-edge adjacency already in source order (k_push_keys_p): a
 // keys-only sort of the window bits moves 8 B per entry and pass instead of 12, and the
 // packing reads the slot from the key instead of gathering the destination.
+// slot(key, k): the destination's row inside its window, of the key at sorted position k.
 struct key_w32 {
+  uint32_t const* rows = nullptr;  // destination by edge position, edge position by sorted position:
+  uint32_t const* vals = nullptr;  // only slot() reads them
+  uint32_t low         = 0;        // 2^win_bits - 1
   __device__ __forceinline__ int64_t win(uint64_t k) const { return (int64_t)(k >> 32); }
   __device__ __forceinline__ uint32_t src(uint64_t k) const { return (uint32_t)k; }
+  __device__ __forceinline__ uint32_t slot(uint64_t, int64_t k) const { return rows[vals[k]] & low; }
 };
 struct key_p {
   int shv, wb;
   uint64_t smask;
   __device__ __forceinline__ int64_t win(uint64_t k) const { return (int64_t)(k >> shv); }
   __device__ __forceinline__ uint32_t src(uint64_t k) const { return (uint32_t)((k >> wb) & smask); }
-  __device__ __forceinline__ uint32_t slot(uint64_t k) const { return (uint32_t)k & ((1u << wb) - 1u); }
+  __device__ __forceinline__ uint32_t slot(uint64_t k, int64_t = 0) const { return (uint32_t)k & ((1u << wb) - 1u); }
 };
 
 // first position of every window w in [0, nwin] among the sorted keys
@@ -1636,42 +1649,15 @@ __global__ __launch_bounds__(256) void k_push_keys_p(E const* off, uint32_t cons
   __shared__ int64_t s_r[2];
   __shared__ E s_off[kRowsTile + 1];
   uint32_t const low = (1u << wb) - 1u;
-  E const* const adj_off = off;
-  if (poff) off = poff;
-  for (int64_t e0 = (int64_t)blockIdx.x * kRowsTile; e0 < ne; e0 += (int64_t)gridDim.x * kRowsTile) {
-    int64_t const e1 = min(e0 + kRowsTile, ne);
-    if (threadIdx.x == 0) {
-      s_r[0] = row_of_edge(off, 0, nv - 1, e0);
-      s_r[1] = row_of_edge(off, s_r[0], nv - 1, e1 - 1);
-    }
-    __syncthreads();
-    int64_t const r0 = s_r[0], r1 = s_r[1];
-    bool const staged = r1 - r0 < kRowsTile;
-    if (staged)
-      for (int64_t i = threadIdx.x; i <= r1 - r0; i += blockDim.x) s_off[i] = off[r0 + i];
-    __syncthreads();
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += blockDim.x) {
-      int64_t r;
-      if (staged) {
-        int64_t lo = 0, hi = r1 - r0;
-        while (lo < hi) {
-          int64_t const mid = (lo + hi + 1) >> 1;
-          if ((int64_t)s_off[mid] <= e) lo = mid;
-          else hi = mid - 1;
-        }
-        r = r0 + lo;
-      } else {
-        r = row_of_edge(off, r0, r1, e);
-      }
-      uint32_t const src = (uint32_t)r;
-      int64_t ea         = e;  // the edge in the adjacency
-      if (poff) ea = (int64_t)adj_off[inv[r]] + (e - (int64_t)(staged ? s_off[r - r0] : off[r]));
-      uint32_t const d = idx[ea];
-      uint64_t const w = (uint64_t)(d >> wb) + (cut && src >= cut ? (uint64_t)nwin_real : 0ull);
-      keys[e]          = (w << shv) | ((uint64_t)src << wb) | (d & low);
-    }
-    __syncthreads();
-  }
+  for (int64_t e0 = (int64_t)blockIdx.x * kRowsTile; e0 < ne; e0 += (int64_t)gridDim.x * kRowsTile)
+    tile_edge_rows(poff ? poff : off, nv, e0, min(e0 + kRowsTile, ne), s_r, s_off,
+                   [&](int64_t e, int64_t r, int64_t first) {
+                     uint32_t const src = (uint32_t)r;
+                     int64_t const ea   = poff ? (int64_t)off[inv[r]] + (e - first) : e;  // the edge in the adjacency
+                     uint32_t const d   = idx[ea];
+                     uint64_t const w   = (uint64_t)(d >> wb) + (cut && src >= cut ? (uint64_t)nwin_real : 0ull);
+                     keys[e]            = (w << shv) | ((uint64_t)src << wb) | (d & low);
+                   });
 }
 
 // unit heads: a window's first entry, every entry at a multiple of kPushUnit (so
@@ -1726,26 +1712,15 @@ __global__ void k_push_pack(uint64_t const* keys, uint32_t const* vals, uint32_t
 // ---- packed 16-bit schedule construction (push_body16)
 // jumps in front of real entry k: its source gap D to the previous entry of the
 // window (0 before the window's first) is coded in the entry when D <= dmax,
-// else by ceil(D / pmax) jumps and an entry of delta 0
-template <typename KC = key_w32>
-__global__ void k_jump_counts(uint64_t const* keys, int64_t ne, int64_t const* ws, uint32_t dmax, uint32_t pmax,
-                              uint32_t* mj, KC kc = {})
-{
-  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < ne; k += (int64_t)gridDim.x * blockDim.x) {
-    int64_t const w     = kc.win(keys[k]);
-    uint32_t const prev = k == ws[w] ? 0u : kc.src(keys[k - 1]);
-    uint32_t const D    = kc.src(keys[k]) - prev;
-    mj[k]               = D > dmax ? (D + pmax - 1) / pmax : 0u;
-  }
-}
-
-// the same count as a scan input (k_jump_counts without the array: the scan reads the
-// keys and writes the prefix in one pass; position ne counts 0)
-struct jump_count_p {
+// else by ceil(D / pmax) jumps and an entry of delta 0.  A scan input: the scan reads
+// the keys and writes the prefix in one pass, without an array of the counts; position
+// ne counts 0
+template <typename KC>
+struct jump_count {
   uint64_t const* keys;
   int64_t const* ws;
   int64_t ne;
-  key_p kc;
+  KC kc;
   uint32_t dmax, pmax;
   __device__ __forceinline__ uint32_t operator()(int64_t k) const
   {
@@ -1759,39 +1734,12 @@ struct jump_count_p {
 };
 
 // real entry k at k + cm[k] (cm = inclusive prefix of the jump counts), its jumps
-// right before it
-__global__ void k_pack16(uint64_t const* keys, uint32_t const* vals, uint32_t const* rows, int64_t ne,
-                         int64_t const* ws, uint32_t const* mj, unsigned long long const* cm,
-                         unsigned long long const* pb, int wb, uint32_t pmax,
-                         uint16_t* ent16)
+// right before it; cm a 32-bit prefix when the edges are below 2^31 (no jump total can
+// wrap it), else 64-bit
+template <typename KC, typename CM>
+__global__ void k_pack16(uint64_t const* keys, int64_t ne, int64_t const* ws, CM const* cm,
+                         unsigned long long const* pb, KC kc, int wb, uint32_t pmax, uint16_t* ent16)
 {
-  uint32_t const jump = (1u << (16 - wb)) - 1, low = (1u << wb) - 1;
-  for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < ne; k += (int64_t)gridDim.x * blockDim.x) {
-    int64_t const w     = (int64_t)(keys[k] >> 32);
-    uint32_t const prev = k == ws[w] ? 0u : (uint32_t)keys[k - 1];
-    uint32_t const D    = (uint32_t)keys[k] - prev;
-    uint32_t const m    = mj[k];
-    int64_t const pos   = k + (int64_t)cm[k] + (int64_t)pb[w];
-    uint32_t const slot = rows[vals[k]] & low;
-    if (m == 0) {
-      ent16[seg_store_index(pos)] = (uint16_t)((D << wb) | slot);
-    } else {
-      for (uint32_t j = 0; j < m; ++j) {
-        uint32_t const pay                  = j + 1 < m ? pmax : D - pmax * (m - 1);
-        ent16[seg_store_index(pos - m + j)] = (uint16_t)((jump << wb) | pay);
-      }
-      ent16[seg_store_index(pos)] = (uint16_t)slot;  // delta 0
-    }
-  }
-}
-
-// the same from key_p keys (the slot in the key); cm a 32-bit prefix when the edges
-// are below 2^31 (no jump total can wrap it), else 64-bit
-template <typename CM>
-__global__ void k_pack16_p(uint64_t const* keys, int64_t ne, int64_t const* ws, CM const* cm,
-                           unsigned long long const* pb, key_p kc, uint32_t pmax, uint16_t* ent16)
-{
-  int const wb        = kc.wb;
   uint32_t const jump = (1u << (16 - wb)) - 1;
   for (int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; k < ne; k += (int64_t)gridDim.x * blockDim.x) {
     uint64_t const key  = keys[k];
@@ -1800,7 +1748,7 @@ __global__ void k_pack16_p(uint64_t const* keys, int64_t ne, int64_t const* ws, 
     uint32_t const D    = kc.src(key) - prev;
     uint32_t const m    = (uint32_t)(cm[k] - cm[k - 1]);  // cm[-1] is the exclusive scan's 0
     int64_t const pos   = k + (int64_t)cm[k] + (int64_t)pb[w];
-    uint32_t const slot = kc.slot(key);
+    uint32_t const slot = kc.slot(key, k);
     if (m == 0) {
       ent16[seg_store_index(pos)] = (uint16_t)((D << wb) | slot);
     } else {
@@ -1841,8 +1789,7 @@ __global__ void k_packed_win_starts(int64_t const* ws, CM const* cm, unsigned lo
 }
 
 // units straight from the padded window starts: window w's units start at nws[w] + j *
-// kPushUnit (what the flag marks + scan + heads below give, without a pass over every
-// packed position)
+// kPushUnit, without a pass over every packed position
 __global__ void k_unit_counts(int64_t const* nws, int64_t nwin, uint32_t* cnt)
 {
   for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w <= nwin; w += (int64_t)gridDim.x * blockDim.x)
@@ -1862,31 +1809,10 @@ __global__ void k_units_direct(int64_t const* nws, int64_t nwin, uint32_t const*
   }
 }
 
-// unit heads: every window start and every kPushUnit entries into a window
-__global__ void k_packed_unit_marks(int64_t const* nws, int64_t nwin, uint32_t* flag)
-{
-  for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nwin; w += (int64_t)gridDim.x * blockDim.x)
-    for (int64_t p = nws[w]; p < nws[w + 1]; p += kPushUnit) flag[p] = 1u;
-}
-__global__ void k_packed_unit_heads(uint32_t const* flag, uint32_t const* uid, int64_t total, int64_t const* nws,
-                                    int64_t nwin, push_unit* units)
-{
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-    if (!flag[p]) continue;
-    int64_t lo = 0, hi = nwin - 1;  // last window with nws[w] <= p
-    while (lo < hi) {
-      int64_t mid = (lo + hi + 1) >> 1;
-      if (nws[mid] <= p) lo = mid;
-      else hi = mid - 1;
-    }
-    units[uid[p]] = push_unit{p, 0, 0, lo};
-  }
-}
-
 // running source before the first entry of every (unit, wave segment)
 template <typename KC, typename CM>
 __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t const* keys, int64_t ne,
-                            int64_t const* ws, uint32_t const* mj, CM const* cm, unsigned long long const* pb,
+                            int64_t const* ws, CM const* cm, unsigned long long const* pb,
                             uint32_t dmax, uint32_t pmax, uint32_t* seg_base, KC kc)
 {
   int64_t const n = nunits * kSegsPerUnit;
@@ -1902,7 +1828,7 @@ __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t con
         else hi = mid;
       }
       int64_t const k     = lo;
-      uint32_t const m    = mj ? mj[k] : (uint32_t)(cm[k] - cm[k - 1]);  // no mj: cm[-1] is the scan's 0
+      uint32_t const m    = (uint32_t)(cm[k] - cm[k - 1]);  // cm[-1] is the exclusive scan's 0
       int64_t const w     = kc.win(keys[k]);
       int64_t const j     = p - (k + (int64_t)cm[k] + (int64_t)pb[w] - m);
       uint32_t const prev = k == ws[w] ? 0u : kc.src(keys[k - 1]);
@@ -2034,15 +1960,17 @@ __global__ __launch_bounds__(kFlagThreads) void k_run_split(uint64_t const* keys
 
 // run key i of window w goes to row position rnws[w] + (i - rws[w]) of the run stream
 // (rnws: window starts padded to whole segments), stored lane-interleaved like a packed
-// segment; the row's first key writes the row's source
-__global__ void k_run_pack(uint64_t const* rk, int64_t nrk, int64_t const* rws, int64_t const* rnws, key_p kc,
+// segment; the row's first key writes the row's source.  (Run keys carry their slot: only
+// the key_p build splits runs off.)
+template <typename KC>
+__global__ void k_run_pack(uint64_t const* rk, int64_t nrk, int64_t const* rws, int64_t const* rnws, KC kc,
                            uint16_t* ent_run, uint32_t* run_src)
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nrk; i += (int64_t)gridDim.x * blockDim.x) {
     uint64_t const key = rk[i];
     int64_t const w    = kc.win(key);
     int64_t const p    = rnws[w] + (i - rws[w]);
-    ent_run[seg_store_index(p)] = (uint16_t)kc.slot(key);
+    ent_run[seg_store_index(p)] = (uint16_t)kc.slot(key, i);
     if ((p & 63) == 0) run_src[p >> 6] = kc.src(key);
   }
 }
@@ -2083,23 +2011,18 @@ inline void mark_whole_items(hipStream_t s, pr_push_t& pp, push_unit* units, std
       else empty.push_back(w);
     }
     if (pp.bands) {
-      pp.win_pub.set_stream(s);
-      pp.win_pub.resize(cnt.size() * sizeof(uint32_t));
+      pp.win_pub.resize(cnt.size() * sizeof(uint32_t), s);
       HIP_CHECK(hipMemsetAsync(pp.win_pub.data(), 0, cnt.size() * sizeof(uint32_t), s));
     }
     pp.nempty = (int64_t)empty.size();
-    pp.win_items.set_stream(s);
-    pp.win_items.resize(cnt.size() * sizeof(uint32_t));
+    pp.win_items.resize(cnt.size() * sizeof(uint32_t), s);
     to_device(pp.win_items.data<uint32_t>(), cnt.data(), cnt.size(), s);
-    pp.win_left.set_stream(s);
-    pp.win_left.resize(cnt.size() * sizeof(uint32_t));
-    pp.empty_wins.set_stream(s);
-    pp.empty_wins.resize(std::max<size_t>(empty.size(), 1) * sizeof(int64_t));
+    pp.win_left.resize(cnt.size() * sizeof(uint32_t), s);
+    pp.empty_wins.resize(std::max<size_t>(empty.size(), 1) * sizeof(int64_t), s);
     if (!empty.empty()) to_device(pp.empty_wins.data<int64_t>(), empty.data(), empty.size(), s);
     HIP_CHECK(hipStreamSynchronize(s));
   }
-  pp.win_multi.set_stream(s);
-  pp.win_multi.resize(multi.size());
+  pp.win_multi.resize(multi.size(), s);
   to_device(pp.win_multi.data<uint8_t>(), multi.data(), multi.size(), s);
   HIP_CHECK(hipStreamSynchronize(s));  // the host vectors go out of scope
 }
@@ -2107,11 +2030,9 @@ inline void mark_whole_items(hipStream_t s, pr_push_t& pp, push_unit* units, std
 inline void upload_items(hipStream_t s, pr_push_t& pp, std::vector<int64_t> const& item_u,
                          std::vector<int64_t> const& queue, int64_t nitems)
 {
-  pp.items.set_stream(s);
-  pp.items.resize(item_u.size() * sizeof(int64_t));
+  pp.items.resize(item_u.size() * sizeof(int64_t), s);
   to_device(pp.items.data<int64_t>(), item_u.data(), item_u.size(), s);
-  pp.queue.set_stream(s);
-  pp.queue.resize(std::max<size_t>(queue.size(), 1) * sizeof(int64_t));
+  pp.queue.resize(std::max<size_t>(queue.size(), 1) * sizeof(int64_t), s);
   to_device(pp.queue.data<int64_t>(), queue.data(), queue.size(), s);
   pp.nitems = nitems;
 }
@@ -2257,6 +2178,194 @@ inline void calibrate_queues(hipStream_t s, pr_push_t& pp, tuning_t const& tu)
   pp.calib = 2;
 }
 
+// before a schedule's first launches: true when the first one is to record the item
+// durations (item_ticks zeroed, calib = 1); otherwise the schedule keeps its queues
+inline bool arm_calibration(pr_push_t& pp, tuning_t const& tu, hipStream_t s)
+{
+  if (!calibration_wanted(pp, tu)) {
+    if (pp.calib == 0) pp.calib = 2;
+    return false;
+  }
+  pp.item_ticks.resize(pp.nitems * sizeof(uint32_t), s);
+  HIP_CHECK(hipMemsetAsync(pp.item_ticks.data(), 0, pp.nitems * sizeof(uint32_t), s));
+  pp.calib = 1;
+  return true;
+}
+
+// after them, on an idle stream: the queues re-dealt by the recorded costs, for the launches to come
+template <typename V, typename E, typename R>
+void redeal_queues(hipStream_t s, pr_push_t& pp, tuning_t const& tu, push_args<V, E, R>& sa)
+{
+  calibrate_queues(s, pp, tu);
+  for (int q = 0; q <= kQueues; ++q) sa.qoff[q] = pp.qoff[q];
+}
+
+// The state every build starts from: the window geometry, zeroed sums and queue heads, no
+// units, items or queues yet, the identity x~ layout and no run rows.  carry: the 32K push's
+// per-destination carry words (packed schedules only).
+inline void reset_push(hipStream_t s, pr_push_t& pp, int wb, int64_t nwin, int64_t nwin_real, bool bands, bool packed)
+{
+  pp.win_bits  = wb;
+  pp.nwin      = nwin;
+  pp.nwin_real = nwin_real;
+  pp.bands     = bands;
+  pp.nacc      = nwin << wb;
+  pp.nunits    = 0;
+  pp.nitems    = 0;
+  pp.qoff.assign(kQueues + 1, 0);
+  pp.packed = packed;
+  pp.acc.resize(pp.nacc * sizeof(unsigned long long), s);
+  HIP_CHECK(hipMemsetAsync(pp.acc.data(), 0, pp.nacc * sizeof(unsigned long long), s));
+  pp.tile_ctr.resize(2 * kQueues * kCtrStride * sizeof(unsigned int), s);  // two sets: iteration parity
+  HIP_CHECK(hipMemsetAsync(pp.tile_ctr.data(), 0, 2 * kQueues * kCtrStride * sizeof(unsigned int), s));
+  pp.carry.release();
+  if (packed && wb == 15) {
+    pp.carry.resize(pp.nacc * sizeof(uint32_t), s);
+    HIP_CHECK(hipMemsetAsync(pp.carry.data(), 0, pp.nacc * sizeof(uint32_t), s));
+  }
+  pp.pos.release();
+  pp.perm_cut   = 0;
+  pp.stream_len = 0;
+  pp.run_src.release();
+  pp.run_rows = pp.run_entries = 0;
+}
+
+template <typename KC>
+void window_starts(hipStream_t s, uint64_t const* keys, int64_t ne, int64_t nwin, KC kc, int64_t* ws)
+{
+  hipLaunchKernelGGL(k_win_starts<KC>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, keys, ne, nwin, ws,
+                     kc);
+  CGX_LAUNCH_CHECK();
+}
+
+// The packed 16-bit schedule from sorted keys, for both builders: keys[0, ne) in (window,
+// source, slot) order under the codec kc, ws their window starts (window_starts), and --
+// key_p only -- the nrk run-row keys at rk_first, in the same order (k_run_split).  Jump
+// counts and their prefix (CM: 32 bits while the entries are below 2^31), the windows padded
+// to whole segments, the stream, the run stream behind it, units, segment bases, items.
+// false, with pp untouched: the stream would take more than 1.5 x the entries (run rows
+// included) or 2^32 positions.
+template <typename KC, typename CM>
+bool assemble_packed(hipStream_t s, uint64_t const* keys, int64_t ne, uint64_t const* rk_first, int64_t nrk, KC kc,
+                     int64_t const* ws, int wb, int64_t nwin, int64_t nwin_real, bool bands, pr_push_t& pp,
+                     tuning_t const& tu)
+{
+  uint32_t const dmax = (1u << (16 - wb)) - 2;  // coded deltas 0 .. dmax; dmax + 1 marks a jump
+  uint32_t const pmax = (1u << wb) - 1;         // jump payloads 1 .. pmax
+  int64_t const ne_all = ne + nrk;
+  dbuf<CM> ex(ne + 1, s);
+  {
+    auto jumps = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0),
+                                                  jump_count<KC>{keys, ws, ne, kc, dmax, pmax});
+    size_t tmp = 0;
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, tmp, jumps, ex.data(), CM(0), (size_t)(ne + 1), rocprim::plus<CM>(), s));
+    buffer t(tmp, s);
+    HIP_CHECK(rocprim::exclusive_scan(t.data(), tmp, jumps, ex.data(), CM(0), (size_t)(ne + 1), rocprim::plus<CM>(), s));
+  }
+  int64_t const total0 = ne + (int64_t)to_host(ex.data() + ne, 1, s)[0];
+  CM const* cm         = ex.data() + 1;  // inclusive prefix
+  // windows padded to whole wave segments (k_packed_pads)
+  dbuf<unsigned long long> pad(nwin + 1, s), pb(nwin + 1, s);
+  hipLaunchKernelGGL(k_packed_pads<CM>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws, cm, nwin,
+                     total0, pad.data());
+  CGX_LAUNCH_CHECK();
+  exclusive_scan<unsigned long long, unsigned long long>(pad.data(), pb.data(), nwin + 1, s);
+  int64_t const total = total0 + (int64_t)to_host(pb.data() + nwin, 1, s)[0];
+  if (std::getenv("CGX_PR_DEBUG"))  // measurement only
+    std::fprintf(stderr, "[pr] schedule: %lld windows of %d bits, %lld entries, %lld of them in run rows, %lld packed entries\n",
+                 (long long)nwin, wb, (long long)ne_all, (long long)nrk, (long long)total);
+  if (!(total + nrk <= ne_all + ne_all / 2 && (uint64_t)total < (1ull << 32))) return false;
+  reset_push(s, pp, wb, nwin, nwin_real, bands, true);
+  pp.stream_len = total;
+  uint16_t const pad_code = (uint16_t)(((1u << (16 - wb)) - 1) << wb);  // a jump of 0: no edge
+  // run stream: after the packed one, from a unit boundary; every window's rows padded to whole
+  // segments (the padding rows' source stays kRunPad); host-side, over the windows
+  std::vector<int64_t> h_rws, h_rnws;
+  int64_t run_off = 0, run_total = 0;
+  dbuf<int64_t> rws;
+  if (nrk) {
+    rws.resize(nwin + 1, s);
+    window_starts(s, rk_first, nrk, nwin, kc, rws.data());
+    h_rws = to_host(rws.data(), (size_t)(nwin + 1), s);
+    h_rnws.assign((size_t)(nwin + 1), 0);
+    for (int64_t w = 0; w < nwin; ++w)
+      h_rnws[w + 1] = h_rnws[w] + (h_rws[w + 1] - h_rws[w] + kSegEntries - 1) / kSegEntries * kSegEntries;
+    run_total       = h_rnws[nwin];
+    run_off         = (total + kPushUnit - 1) / kPushUnit * kPushUnit;
+    pp.run_rows     = nrk / 64;
+    pp.run_entries  = nrk;
+  }
+  int64_t const ent_len = (nrk ? run_off + run_total : total) + kPushUnit;  // + a unit: the kernel prefetches whole units
+  pp.ent16.resize(ent_len * sizeof(uint16_t), s);
+  fill<uint16_t>(pp.ent16.data<uint16_t>(), (size_t)ent_len, pad_code, s);
+  if (nrk) {
+    int64_t const nrows = run_total / 64 + kPushUnit / 64;  // + a unit's rows: short units' idle waves read on
+    pp.run_src.resize(nrows * sizeof(uint32_t), s);
+    fill<uint32_t>(pp.run_src.data<uint32_t>(), (size_t)nrows, kRunPad, s);
+    dbuf<int64_t> rnws(nwin + 1, s);
+    to_device(rnws.data(), h_rnws.data(), h_rnws.size(), s);
+    hipLaunchKernelGGL(k_run_pack<KC>, dim3(grid_for(nrk, kBlock, 16384)), dim3(kBlock), 0, s, rk_first, nrk,
+                       rws.data(), rnws.data(), kc, pp.ent16.data<uint16_t>() + run_off, pp.run_src.data<uint32_t>());
+    CGX_LAUNCH_CHECK();
+    HIP_CHECK(hipStreamSynchronize(s));  // (h_rnws is pageable: the copy has read it)
+  }
+  if (ne)
+    hipLaunchKernelGGL((k_pack16<KC, CM>), dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys, ne, ws, cm,
+                       pb.data(), kc, wb, pmax, pp.ent16.data<uint16_t>());
+  CGX_LAUNCH_CHECK();
+  dbuf<int64_t> nws(nwin + 1, s);
+  hipLaunchKernelGGL(k_packed_win_starts<CM>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws, cm,
+                     pb.data(), nwin, total0, nws.data());
+  CGX_LAUNCH_CHECK();
+  int64_t nunits   = 0;
+  push_unit* units = nullptr;
+  if (nrk) {
+    // a window's run units, then its packed units (an item is a range of units): on the host,
+    // from the two sets of window starts.  The packed units are what k_units_direct and
+    // k_unit_ends below give for the same starts ([nws[w] + j kPushUnit, the next unit or
+    // window start), base 0): keep the two in step.
+    auto const h_nws = to_host(nws.data(), (size_t)(nwin + 1), s);
+    std::vector<push_unit> hu;
+    for (int64_t w = 0; w < nwin; ++w) {
+      for (int64_t p = h_rnws[w]; p < h_rnws[w + 1]; p += kPushUnit)
+        hu.push_back(push_unit{run_off + p, run_off + std::min<int64_t>(p + kPushUnit, h_rnws[w + 1]), ~(p / 64), w});
+      for (int64_t p = h_nws[w]; p < h_nws[w + 1]; p += kPushUnit)
+        hu.push_back(push_unit{p, std::min<int64_t>(p + kPushUnit, h_nws[w + 1]), 0, w});
+    }
+    nunits = (int64_t)hu.size();
+    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit), s);
+    units = pp.units.data<push_unit>();
+    to_device(units, hu.data(), hu.size(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+  } else {
+    dbuf<uint32_t> ucnt(nwin + 1, s), upos(nwin + 1, s);
+    hipLaunchKernelGGL(k_unit_counts, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
+                       ucnt.data());
+    CGX_LAUNCH_CHECK();
+    exclusive_scan<uint32_t, uint32_t>(ucnt.data(), upos.data(), nwin + 1, s);
+    nunits = (int64_t)to_host(upos.data() + nwin, 1, s)[0];
+    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit), s);
+    units = pp.units.data<push_unit>();
+    if (nunits)
+      hipLaunchKernelGGL(k_units_direct, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
+                         upos.data(), nunits, units);
+    CGX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, total);
+    CGX_LAUNCH_CHECK();
+  }
+  pp.seg_base.resize(std::max<int64_t>(nunits * kSegsPerUnit, 1) * sizeof(uint32_t), s);
+  if (nunits)
+    hipLaunchKernelGGL((k_seg_bases<KC, CM>), dim3(grid_for(nunits * kSegsPerUnit, kBlock, 16384)), dim3(kBlock), 0,
+                       s, units, nunits, keys, ne, ws, cm, pb.data(), dmax, pmax, pp.seg_base.data<uint32_t>(), kc);
+  CGX_LAUNCH_CHECK();
+  pp.ent.release();
+  pp.ew.release();
+  build_items(s, pp, units, nunits, wb >= 13, tu);
+  pp.nunits = nunits;
+  HIP_CHECK(hipStreamSynchronize(s));
+  return true;
+}
+
 // Push schedule of an edge list given as (row = destination, col = source) with
 // destinations in [0, n_rows) and sources in [0, n_cols) -- the SG pull adjacency
 // or one MG 2D block.  col_sorted: the list is in (source, destination) order (the
@@ -2284,27 +2393,12 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
   int const wb = push_win_bits(n_rows, tu, wide && !w && tu.pr_packed);
   int const sb = 32 - wb;
   if (wb != 14 || w || !tu.pr_packed || band_cut >= n_cols) band_cut = 0;
-  pp.carry.release();
-  pp.pos.release();  // (the identity layout: build_x_layout is the symmetric packed build's)
-  pp.perm_cut   = 0;
-  pp.stream_len = 0;
   int64_t const nwin_real = std::max<int64_t>(1, (n_rows + (int64_t(1) << wb) - 1) >> wb);
   int64_t const nwin      = band_cut > 0 ? 2 * nwin_real : nwin_real;
-  pp.win_bits        = wb;
-  pp.nwin            = nwin;
-  pp.bands           = band_cut > 0;
-  pp.nwin_real       = nwin_real;
-  pp.nacc            = nwin << wb;
-  pp.acc.set_stream(s);
-  pp.acc.resize(pp.nacc * sizeof(unsigned long long));
-  HIP_CHECK(hipMemsetAsync(pp.acc.data(), 0, pp.nacc * sizeof(unsigned long long), s));
-  pp.tile_ctr.set_stream(s);
-  pp.tile_ctr.resize(2 * kQueues * kCtrStride * sizeof(unsigned int));  // two sets: iteration parity
-  HIP_CHECK(hipMemsetAsync(pp.tile_ctr.data(), 0, 2 * kQueues * kCtrStride * sizeof(unsigned int), s));
-  pp.nunits = 0;
-  pp.nitems = 0;
-  pp.qoff.assign(kQueues + 1, 0);
-  if (ne == 0) return;
+  if (ne == 0) {
+    reset_push(s, pp, wb, nwin, nwin_real, band_cut > 0, false);
+    return;
+  }
   dbuf<uint64_t> keys_out(ne, s);
   dbuf<uint32_t> vals_out(ne, s);
   {
@@ -2318,79 +2412,13 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
                                          32 + bits_for((unsigned long long)std::max<int64_t>(nwin - 1, 1)), s);
   }
   dbuf<int64_t> ws(nwin + 1, s);
-  hipLaunchKernelGGL(k_win_starts<key_w32>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s,
-                     keys_out.data(), ne, nwin, ws.data(), key_w32{});
-  CGX_LAUNCH_CHECK();
-  pp.packed = false;
+  window_starts(s, keys_out.data(), ne, nwin, key_w32{}, ws.data());
   if (!w && tu.pr_packed) {  // 16-bit entries unless the jumps would grow the entries by more than half
-    uint32_t const dmax = (1u << (16 - wb)) - 2;  // coded deltas 0 .. dmax; dmax + 1 marks a jump
-    uint32_t const pmax = (1u << wb) - 1;         // jump payloads 1 .. pmax
-    dbuf<uint32_t> mj(ne + 1, s);
-    dbuf<unsigned long long> ex(ne + 1, s);
-    hipLaunchKernelGGL(k_jump_counts<key_w32>, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s,
-                       keys_out.data(), ne, ws.data(), dmax, pmax, mj.data(), key_w32{});
-    CGX_LAUNCH_CHECK();
-    fill<uint32_t>(mj.data() + ne, 1, 0u, s);
-    exclusive_scan<uint32_t, unsigned long long>(mj.data(), ex.data(), ne + 1, s);
-    int64_t const total0 = ne + (int64_t)to_host(ex.data() + ne, 1, s)[0];
-    unsigned long long const* cm = ex.data() + 1;  // inclusive prefix
-    // windows padded to whole wave segments (k_packed_pads)
-    dbuf<unsigned long long> pad(nwin + 1, s), pb(nwin + 1, s);
-    hipLaunchKernelGGL(k_packed_pads<unsigned long long>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws.data(), cm, nwin,
-                       total0, pad.data());
-    CGX_LAUNCH_CHECK();
-    exclusive_scan<unsigned long long, unsigned long long>(pad.data(), pb.data(), nwin + 1, s);
-    int64_t const total = total0 + (int64_t)to_host(pb.data() + nwin, 1, s)[0];
-    if (std::getenv("CGX_PR_DEBUG"))  // measurement only
-      std::fprintf(stderr, "[pr] schedule: %lld rows, %lld sources, %lld edges, %d-bit windows, %lld packed entries\n",
-                   (long long)n_rows, (long long)n_cols, (long long)ne, wb, (long long)total);
-    if (total <= ne + ne / 2 && (uint64_t)total < (1ull << 32)) {
-      uint16_t const pad_code = (uint16_t)(((1u << (16 - wb)) - 1) << wb);  // a jump of 0: no edge
-      pp.packed     = true;
-      pp.stream_len = total;
-      if (wb == 15) {  // the 32K push's per-destination carry words
-        pp.carry.set_stream(s);
-        pp.carry.resize(pp.nacc * sizeof(uint32_t));
-        HIP_CHECK(hipMemsetAsync(pp.carry.data(), 0, pp.nacc * sizeof(uint32_t), s));
-      }
-      pp.ent16.set_stream(s);
-      pp.ent16.resize((total + kPushUnit) * sizeof(uint16_t));  // + a unit: the kernel prefetches whole units
-      fill<uint16_t>(pp.ent16.data<uint16_t>(), (size_t)(total + kPushUnit), pad_code, s);
-      hipLaunchKernelGGL(k_pack16, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys_out.data(),
-                         vals_out.data(), rows, ne, ws.data(), mj.data(), cm, pb.data(), wb, pmax,
-                         pp.ent16.data<uint16_t>());
-      CGX_LAUNCH_CHECK();
-      dbuf<int64_t> nws(nwin + 1, s);
-      hipLaunchKernelGGL(k_packed_win_starts<unsigned long long>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws.data(),
-                         cm, pb.data(), nwin, total0, nws.data());
-      dbuf<uint32_t> pflag(total + 1, s), puid(total + 1, s);
-      fill<uint32_t>(pflag.data(), (size_t)(total + 1), 0u, s);
-      hipLaunchKernelGGL(k_packed_unit_marks, dim3(grid_for(nwin, 64, 4096)), dim3(64), 0, s, nws.data(), nwin,
-                         pflag.data());
-      CGX_LAUNCH_CHECK();
-      exclusive_scan<uint32_t, uint32_t>(pflag.data(), puid.data(), total + 1, s);
-      int64_t const nunits = (int64_t)to_host(puid.data() + total, 1, s)[0];
-      pp.units.set_stream(s);
-      pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
-      push_unit* units = pp.units.data<push_unit>();
-      hipLaunchKernelGGL(k_packed_unit_heads, dim3(grid_for(total, kBlock, 16384)), dim3(kBlock), 0, s, pflag.data(),
-                         puid.data(), total, nws.data(), nwin, units);
-      CGX_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, total);
-      CGX_LAUNCH_CHECK();
-      pp.seg_base.set_stream(s);
-      pp.seg_base.resize(std::max<int64_t>(nunits * kSegsPerUnit, 1) * sizeof(uint32_t));
-      hipLaunchKernelGGL((k_seg_bases<key_w32, unsigned long long>), dim3(grid_for(nunits * kSegsPerUnit, kBlock, 16384)), dim3(kBlock), 0, s, units,
-                         nunits, keys_out.data(), ne, ws.data(), mj.data(), cm, pb.data(), dmax, pmax,
-                         pp.seg_base.data<uint32_t>(), key_w32{});
-      CGX_LAUNCH_CHECK();
-      pp.ent.release();
-      pp.ew.release();
-      build_items(s, pp, units, nunits, wb >= 13, tu);
-      pp.nunits = nunits;
-      HIP_CHECK(hipStreamSynchronize(s));
+    auto const assemble = ne < (int64_t(1) << 31) ? assemble_packed<key_w32, uint32_t>
+                                                  : assemble_packed<key_w32, unsigned long long>;
+    if (assemble(s, keys_out.data(), ne, nullptr, 0, key_w32{rows, vals_out.data(), (1u << wb) - 1}, ws.data(), wb, nwin,
+                 nwin_real, band_cut > 0, pp, tu))
       return;
-    }
   }
   if (band_cut > 0 || wb == 15) {  // bands and 32K windows need the packed format: the schedule without them
     keys_out.free();
@@ -2399,6 +2427,7 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
     build_push_from_coo<C, R>(s, rows, cols, w, ne, n_rows, n_cols, pp, tu, col_sorted, 0, false);
     return;
   }
+  reset_push(s, pp, wb, nwin, nwin_real, false, false);
   dbuf<uint32_t> flag(ne + 1, s), uid(ne + 1, s);
   hipLaunchKernelGGL(k_unit_flags, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys_out.data(), ne,
                      ws.data(), sb, flag.data());
@@ -2406,20 +2435,17 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
   fill<uint32_t>(flag.data() + ne, 1, 0u, s);
   exclusive_scan<uint32_t, uint32_t>(flag.data(), uid.data(), ne + 1, s);
   int64_t const nunits = (int64_t)to_host(uid.data() + ne, 1, s)[0];
-  pp.units.set_stream(s);
-  pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
+  pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit), s);
   push_unit* units = pp.units.data<push_unit>();
   hipLaunchKernelGGL(k_unit_heads, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys_out.data(),
                      flag.data(), uid.data(), ne, units);
   CGX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, ne);
   CGX_LAUNCH_CHECK();
-  pp.ent.set_stream(s);
-  pp.ent.resize((ne + kPushUnit) * sizeof(uint32_t));  // padded: the kernel loads whole units
+  pp.ent.resize((ne + kPushUnit) * sizeof(uint32_t), s);  // padded: the kernel loads whole units
   HIP_CHECK(hipMemsetAsync(pp.ent.data<uint32_t>() + ne, 0, kPushUnit * sizeof(uint32_t), s));
-  pp.ew.set_stream(s);
   if (w) {
-    pp.ew.resize((ne + kPushUnit) * sizeof(R));  // padded like ent
+    pp.ew.resize((ne + kPushUnit) * sizeof(R), s);  // padded like ent
     HIP_CHECK(hipMemsetAsync(pp.ew.data<R>() + ne, 0, kPushUnit * sizeof(R), s));
   } else {
     pp.ew.release();
@@ -2527,10 +2553,10 @@ __global__ void k_layout_finish(E const* off, uint32_t const* tail, int64_t cut,
   }
 }
 
-// pos into pp.pos, inv and the offsets of the rows in position order for the key pass
+// pos, inv and the offsets of the rows in position order for the key pass
 template <typename E>
 void build_x_layout(hipStream_t s, E const* off, uint32_t const* idx, int64_t nv, int wb, int64_t cut, int span,
-                    pr_push_t& pp, dbuf<uint32_t>& inv, dbuf<E>& poff)
+                    buffer& pos, dbuf<uint32_t>& inv, dbuf<E>& poff)
 {
   int64_t const n    = nv - cut;
   int64_t const nwin = (nv + (int64_t(1) << wb) - 1) >> wb;
@@ -2545,25 +2571,25 @@ void build_x_layout(hipStream_t s, E const* off, uint32_t const* idx, int64_t nv
   // (stable: equal keys keep their id order)
   bool const in1 = radix_sort_pairs_db<uint64_t, uint32_t>(k0.data(), k1.data(), v0.data(), v1.data(), (size_t)n, 0,
                                                            rb + 2 * vb, s);
-  pp.pos.set_stream(s);
-  pp.pos.resize(nv * sizeof(uint32_t));
+  pos.resize(nv * sizeof(uint32_t), s);
   inv.resize(nv, s);
   poff.resize(nv + 1, s);
   hipLaunchKernelGGL(k_layout_finish<E>, dim3(grid_for(nv + 1, kBlock, 4096)), dim3(kBlock), 0, s, off,
-                     in1 ? v1.data() : v0.data(), cut, nv, pp.pos.data<uint32_t>(), inv.data(), poff.data());
+                     in1 ? v1.data() : v0.data(), cut, nv, pos.data<uint32_t>(), inv.data(), poff.data());
   CGX_LAUNCH_CHECK();
   exclusive_scan<E, E>(poff.data(), poff.data(), (size_t)(nv + 1), s);  // the degrees to offsets, in place
 }
 
-// The packed schedule of a symmetric unweighted graph straight from its adjacency
-// (build_push_from_coo's packed path with key_p keys; same stream, units, bases and
-// items bit for bit): one word per entry through a keys-only sort of the window bits,
-// no destination gather while packing, units from the window starts.  RMAT-24's first
-// call spent 29 ms in the general build.  false: the keys do not fit a word or the
-// stream would not pack -- nothing built, the caller takes the general path.
-template <typename E, typename CM>
-bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, int64_t ne, int64_t nv, pr_push_t& pp,
-                              tuning_t const& tu, int64_t band_cut, bool wide, bool runs_ok)
+// The packed schedule of a symmetric unweighted graph straight from its adjacency:
+// key_p keys, one word per entry, through a keys-only sort of the window bits, the x~
+// layout in front of the keys and the run split behind the sort; then assemble_packed, as
+// build_push_from_coo's packed path (without layout and runs: the same stream, units, bases
+// and items bit for bit).  RMAT-24's first call spent 29 ms in the general build.  false:
+// the keys do not fit a word or the stream would not pack -- nothing built, the caller
+// takes the general path.
+template <typename E>
+bool build_push_packed_sym(hipStream_t s, E const* off, uint32_t const* idx, int64_t ne, int64_t nv, pr_push_t& pp,
+                           tuning_t const& tu, int64_t band_cut, bool wide, bool runs_ok)
 {
   int const wb = push_win_bits(nv, tu, wide);
   if (wb != 14 || band_cut >= nv) band_cut = 0;
@@ -2574,19 +2600,19 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
   int const shv   = wb + sbits;
   if (shv + vbits > 64 || (uint64_t)ne >= (1ull << 32) || (uint64_t)nv >= (1ull << 32)) return false;
   key_p const kc{shv, wb, (sbits >= 32 ? ~0ull : ((1ull << sbits) - 1ull))};
-  uint32_t const dmax = (1u << (16 - wb)) - 2, pmax = (1u << wb) - 1;
-  // x~ layout: unbanded schedules, from a cut of at least one window (the hub table stays below it)
+  // x~ layout: unbanded schedules, from a cut of at least one window (the hub table stays below
+  // it); pp takes it once the stream has packed
+  buffer pos;
+  int64_t perm_cut = 0;
   dbuf<uint32_t> inv;
   dbuf<E> poff;
-  pp.pos.release();
-  pp.perm_cut = 0;
   if (band_cut == 0 && ne && push_perm_on(wb, tu)) {
     int64_t const win = int64_t(1) << wb;
     int64_t cut       = std::min<int64_t>(std::max<int64_t>(tu.pr_perm_cut >= 0 ? tu.pr_perm_cut : kPermCut, 1), nv);
     cut               = (cut + win - 1) / win * win;
     if (cut < nv) {
-      build_x_layout<E>(s, off, idx, nv, wb, cut, push_perm_span(wb, tu), pp, inv, poff);
-      pp.perm_cut = cut;
+      build_x_layout<E>(s, off, idx, nv, wb, cut, push_perm_span(wb, tu), pos, inv, poff);
+      perm_cut = cut;
     }
   }
   dbuf<uint64_t> kbuf(std::max<int64_t>(ne, 1), s);
@@ -2595,8 +2621,7 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
     if (ne) {
       hipLaunchKernelGGL(k_push_keys_p<E>, dim3((unsigned)std::min<int64_t>((ne + kRowsTile - 1) / kRowsTile, 65536)),
                          dim3(256), 0, s, off, idx, nv, ne, wb, shv, (uint32_t)band_cut, nwin_real, kbuf.data(),
-                         pp.perm_cut ? poff.data() : (E const*)nullptr,
-                         pp.perm_cut ? inv.data() : (uint32_t const*)nullptr);
+                         perm_cut ? poff.data() : (E const*)nullptr, perm_cut ? inv.data() : (uint32_t const*)nullptr);
       CGX_LAUNCH_CHECK();
       inv.free();
       poff.free();
@@ -2634,161 +2659,16 @@ bool build_push_packed_sym_cm(hipStream_t s, E const* off, uint32_t const* idx, 
       ne       = npk;
     }
   }
-  uint64_t const* keys = kbuf.data();
   dbuf<int64_t> ws(nwin + 1, s);
-  hipLaunchKernelGGL(k_win_starts<key_p>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, keys, ne, nwin,
-                     ws.data(), kc);
-  CGX_LAUNCH_CHECK();
-  dbuf<CM> ex(ne + 1, s);
-  {
-    auto jumps = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int64_t>(0),
-                                                  jump_count_p{keys, ws.data(), ne, kc, dmax, pmax});
-    size_t tmp = 0;
-    HIP_CHECK(rocprim::exclusive_scan(nullptr, tmp, jumps, ex.data(), CM(0), (size_t)(ne + 1), rocprim::plus<CM>(), s));
-    buffer t(tmp, s);
-    HIP_CHECK(rocprim::exclusive_scan(t.data(), tmp, jumps, ex.data(), CM(0), (size_t)(ne + 1), rocprim::plus<CM>(), s));
-  }
-  int64_t const total0 = ne + (int64_t)to_host(ex.data() + ne, 1, s)[0];
-  CM const* cm         = ex.data() + 1;  // inclusive prefix
-  dbuf<unsigned long long> pad(nwin + 1, s), pb(nwin + 1, s);
-  hipLaunchKernelGGL(k_packed_pads<CM>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws.data(), cm, nwin,
-                     total0, pad.data());
-  CGX_LAUNCH_CHECK();
-  exclusive_scan<unsigned long long, unsigned long long>(pad.data(), pb.data(), nwin + 1, s);
-  int64_t const total = total0 + (int64_t)to_host(pb.data() + nwin, 1, s)[0];
-  if (!(total + nrk <= ne_all + ne_all / 2 && (uint64_t)total < (1ull << 32))) {  // (of all entries, run rows included)
-    pp.pos.release();
-    pp.perm_cut = 0;
-    return false;
-  }
-  pp.built      = true;
-  pp.ok         = true;
-  pp.stream_len = total;
-  pp.win_bits   = wb;
-  pp.nwin      = nwin;
-  pp.bands     = band_cut > 0;
-  pp.nwin_real = nwin_real;
-  pp.nacc      = nwin << wb;
-  pp.acc.set_stream(s);
-  pp.acc.resize(pp.nacc * sizeof(unsigned long long));
-  HIP_CHECK(hipMemsetAsync(pp.acc.data(), 0, pp.nacc * sizeof(unsigned long long), s));
-  pp.tile_ctr.set_stream(s);
-  pp.tile_ctr.resize(2 * kQueues * kCtrStride * sizeof(unsigned int));
-  HIP_CHECK(hipMemsetAsync(pp.tile_ctr.data(), 0, 2 * kQueues * kCtrStride * sizeof(unsigned int), s));
-  pp.carry.release();
-  if (wb == 15) {
-    pp.carry.set_stream(s);
-    pp.carry.resize(pp.nacc * sizeof(uint32_t));
-    HIP_CHECK(hipMemsetAsync(pp.carry.data(), 0, pp.nacc * sizeof(uint32_t), s));
-  }
-  pp.qoff.assign(kQueues + 1, 0);
-  pp.nitems = 0;
-  pp.packed = true;
-  uint16_t const pad_code = (uint16_t)(((1u << (16 - wb)) - 1) << wb);  // a jump of 0: no edge
-  // run stream: after the packed one, from a unit boundary; every window's rows padded to whole
-  // segments (the padding rows' source stays kRunPad); host-side, over the windows
-  std::vector<int64_t> h_rws, h_rnws;
-  int64_t run_off = 0, run_total = 0;
-  pp.run_rows = pp.run_entries = 0;
-  pp.run_src.release();
-  dbuf<int64_t> rws;
-  if (nrk) {
-    rws.resize(nwin + 1, s);
-    hipLaunchKernelGGL(k_win_starts<key_p>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, rk_first,
-                       nrk, nwin, rws.data(), kc);
-    CGX_LAUNCH_CHECK();
-    h_rws = to_host(rws.data(), (size_t)(nwin + 1), s);
-    h_rnws.assign((size_t)(nwin + 1), 0);
-    for (int64_t w = 0; w < nwin; ++w)
-      h_rnws[w + 1] = h_rnws[w] + (h_rws[w + 1] - h_rws[w] + kSegEntries - 1) / kSegEntries * kSegEntries;
-    run_total       = h_rnws[nwin];
-    run_off         = (total + kPushUnit - 1) / kPushUnit * kPushUnit;
-    pp.run_rows     = nrk / 64;
-    pp.run_entries  = nrk;
-  }
-  int64_t const ent_len = (nrk ? run_off + run_total : total) + kPushUnit;  // + a unit: the kernel prefetches whole units
-  pp.ent16.set_stream(s);
-  pp.ent16.resize(ent_len * sizeof(uint16_t));
-  fill<uint16_t>(pp.ent16.data<uint16_t>(), (size_t)ent_len, pad_code, s);
-  if (nrk) {
-    int64_t const nrows = run_total / 64 + kPushUnit / 64;  // + a unit's rows: short units' idle waves read on
-    pp.run_src.set_stream(s);
-    pp.run_src.resize(nrows * sizeof(uint32_t));
-    fill<uint32_t>(pp.run_src.data<uint32_t>(), (size_t)nrows, kRunPad, s);
-    dbuf<int64_t> rnws(nwin + 1, s);
-    to_device(rnws.data(), h_rnws.data(), h_rnws.size(), s);
-    hipLaunchKernelGGL(k_run_pack, dim3(grid_for(nrk, kBlock, 16384)), dim3(kBlock), 0, s, rk_first, nrk, rws.data(),
-                       rnws.data(), kc, pp.ent16.data<uint16_t>() + run_off, pp.run_src.data<uint32_t>());
-    CGX_LAUNCH_CHECK();
-    HIP_CHECK(hipStreamSynchronize(s));  // (h_rnws is pageable: the copy has read it)
-  }
-  if (ne)
-    hipLaunchKernelGGL(k_pack16_p<CM>, dim3(grid_for(ne, kBlock, 16384)), dim3(kBlock), 0, s, keys, ne, ws.data(),
-                       cm, pb.data(), kc, pmax, pp.ent16.data<uint16_t>());
-  CGX_LAUNCH_CHECK();
-  dbuf<int64_t> nws(nwin + 1, s);
-  hipLaunchKernelGGL(k_packed_win_starts<CM>, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, ws.data(),
-                     cm, pb.data(), nwin, total0, nws.data());
-  CGX_LAUNCH_CHECK();
-  int64_t nunits   = 0;
-  push_unit* units = nullptr;
-  pp.units.set_stream(s);
-  if (nrk) {
-    // a window's run units, then its packed units (an item is a range of units): on the host,
-    // from the two sets of window starts.  The packed units are what k_units_direct and
-    // k_unit_ends below give for the same starts ([nws[w] + j kPushUnit, the next unit or
-    // window start), base 0): keep the two in step.
-    auto const h_nws = to_host(nws.data(), (size_t)(nwin + 1), s);
-    std::vector<push_unit> hu;
-    for (int64_t w = 0; w < nwin; ++w) {
-      for (int64_t p = h_rnws[w]; p < h_rnws[w + 1]; p += kPushUnit)
-        hu.push_back(push_unit{run_off + p, run_off + std::min<int64_t>(p + kPushUnit, h_rnws[w + 1]), ~(p / 64), w});
-      for (int64_t p = h_nws[w]; p < h_nws[w + 1]; p += kPushUnit)
-        hu.push_back(push_unit{p, std::min<int64_t>(p + kPushUnit, h_nws[w + 1]), 0, w});
-    }
-    nunits = (int64_t)hu.size();
-    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
-    units = pp.units.data<push_unit>();
-    to_device(units, hu.data(), hu.size(), s);
-    HIP_CHECK(hipStreamSynchronize(s));
-  } else {
-    dbuf<uint32_t> ucnt(nwin + 1, s), upos(nwin + 1, s);
-    hipLaunchKernelGGL(k_unit_counts, dim3(grid_for(nwin + 1, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
-                       ucnt.data());
-    CGX_LAUNCH_CHECK();
-    exclusive_scan<uint32_t, uint32_t>(ucnt.data(), upos.data(), nwin + 1, s);
-    nunits = (int64_t)to_host(upos.data() + nwin, 1, s)[0];
-    pp.units.resize(std::max<int64_t>(nunits, 1) * sizeof(push_unit));
-    units = pp.units.data<push_unit>();
-    if (nunits)
-      hipLaunchKernelGGL(k_units_direct, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, nws.data(), nwin,
-                         upos.data(), nunits, units);
-    CGX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_unit_ends, dim3(grid_for(nunits, kBlock, 4096)), dim3(kBlock), 0, s, units, nunits, total);
-    CGX_LAUNCH_CHECK();
-  }
-  pp.seg_base.set_stream(s);
-  pp.seg_base.resize(std::max<int64_t>(nunits * kSegsPerUnit, 1) * sizeof(uint32_t));
-  if (nunits)
-    hipLaunchKernelGGL((k_seg_bases<key_p, CM>), dim3(grid_for(nunits * kSegsPerUnit, kBlock, 16384)), dim3(kBlock), 0,
-                       s, units, nunits, keys, ne, ws.data(), (uint32_t const*)nullptr, cm, pb.data(), dmax, pmax,
-                       pp.seg_base.data<uint32_t>(), kc);
-  CGX_LAUNCH_CHECK();
-  pp.ent.release();
-  pp.ew.release();
-  build_items(s, pp, units, nunits, wb >= 13, tu);
-  pp.nunits = nunits;
-  HIP_CHECK(hipStreamSynchronize(s));
+  window_starts(s, kbuf.data(), ne, nwin, kc, ws.data());
+  auto const assemble = ne_all < (int64_t(1) << 31) ? assemble_packed<key_p, uint32_t>
+                                                    : assemble_packed<key_p, unsigned long long>;
+  if (!assemble(s, kbuf.data(), ne, rk_first, nrk, kc, ws.data(), wb, nwin, nwin_real, band_cut > 0, pp, tu)) return false;
+  pp.built    = true;
+  pp.ok       = true;
+  pp.pos      = std::move(pos);
+  pp.perm_cut = perm_cut;
   return true;
-}
-
-template <typename E>
-bool build_push_packed_sym(hipStream_t s, E const* off, uint32_t const* idx, int64_t ne, int64_t nv, pr_push_t& pp,
-                           tuning_t const& tu, int64_t band_cut, bool wide, bool runs_ok)
-{
-  if (ne < (int64_t(1) << 31))
-    return build_push_packed_sym_cm<E, uint32_t>(s, off, idx, ne, nv, pp, tu, band_cut, wide, runs_ok);
-  return build_push_packed_sym_cm<E, unsigned long long>(s, off, idx, ne, nv, pp, tu, band_cut, wide, runs_ok);
 }
 
 template <typename V, typename E, typename R>
@@ -2860,6 +2740,45 @@ dbuf<V> internal_ids(handle_t& h, graph_t& g, array_view_t const* ext)
   renumber_ext_to_int(h, g, ids.data(), ext->size, true);
   return ids;
 }
+
+inline void check_alpha_eps(double alpha, double eps)
+{
+  CGX_INPUT(alpha >= 0.0 && alpha <= 1.0, "Invalid input argument: alpha should be in [0.0, 1.0].");
+  CGX_INPUT(eps >= 0.0, "Invalid input argument: epsilon should be non-negative.");
+}
+
+// Profiling: one pair of pooled HIP events around each chunk of iterations -- an event
+// between every two iterations cost a ~10 us queue gap per iteration -- and chunk time /
+// iterations run as the result, so the no-op launches after convergence in the last chunk
+// count against the kernels.
+struct chunk_timer {
+  handle_t& h;
+  hipStream_t s;
+  std::vector<hipEvent_t> ev;
+  void begin()
+  {
+    if (!h.profiling) return;
+    ev.push_back(h.event(ev.size()));  // pooled on the handle
+    ev.push_back(h.event(ev.size()));
+    HIP_CHECK(hipEventRecord(ev[ev.size() - 2], s));
+  }
+  void end()
+  {
+    if (h.profiling) HIP_CHECK(hipEventRecord(ev.back(), s));
+  }
+  void report(int iters)  // after the last chunk's host synchronisation
+  {
+    if (!h.profiling) return;
+    double tot = 0;
+    for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      tot += ms;
+    }
+    h.last_hot_ms       = tot;
+    h.last_hot_launches = std::max<size_t>((size_t)iters, 1);
+  }
+};
 
 template <typename V, typename E, typename R>
 void set_queue_args(push_args<V, E, R>& sa, pr_push_t& pp, hipStream_t s)
@@ -2936,8 +2855,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
                    centrality_result_t& res)
 {
   hipStream_t s = h.stream;
-  CGX_INPUT(alpha >= 0.0 && alpha <= 1.0, "Invalid input argument: alpha should be in [0.0, 1.0].");
-  CGX_INPUT(eps >= 0.0, "Invalid input argument: epsilon should be non-negative.");
+  check_alpha_eps(alpha, eps);
   CGX_INPUT((pers_v == nullptr) == (pers_s == nullptr) && (!pers_v || pers_v->size == pers_s->size),
             "Invalid input argument: personalization vertices and values must be given together.");
   CGX_INPUT((guess_v == nullptr) == (guess_s == nullptr), "Invalid input argument: initial guess vertices and values must be given together.");
@@ -3080,15 +2998,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
     sa.nhub    = h.tune.pr_hub ? nv : 0;  // hub x~ staged in LDS (16K windows; A/B switch)
   }
   // measured-cost queues: the first launch on this schedule records item durations
-  bool calibrating = push && calibration_wanted(adj.pr, h.tune);
-  if (calibrating) {
-    adj.pr.item_ticks.set_stream(s);
-    adj.pr.item_ticks.resize(adj.pr.nitems * sizeof(uint32_t));
-    HIP_CHECK(hipMemsetAsync(adj.pr.item_ticks.data(), 0, adj.pr.nitems * sizeof(uint32_t), s));
-    adj.pr.calib = 1;
-  } else if (push && adj.pr.calib == 0) {
-    adj.pr.calib = 2;
-  }
+  bool calibrating = push && arm_calibration(adj.pr, h.tune, s);
   // CGX_PR_TIMELINE=<file>: per-item timeline of the packed push (measurement only)
   char const* tl_path = push ? std::getenv("CGX_PR_TIMELINE") : nullptr;
   dbuf<unsigned long long> tl;
@@ -3099,11 +3009,8 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
     sa.tl = tl.data();
   }
   // Chunked enqueue (next_chunk): a host check after 8 iterations, then after the
-  // predicted remainder.  Profiling records one pair of pooled HIP events around each chunk -- an event
-  // between every two iterations cost a ~10 us queue gap per iteration -- and
-  // reports chunk time / iterations run, so the no-op launches after convergence
-  // in the last chunk count against the kernels.
-  std::vector<hipEvent_t> ev;
+  // predicted remainder; profiling times the chunks (chunk_timer)
+  chunk_timer timer{h, s, {}};
   pr_state hst{};
   R* bufs[2]    = {xa.data(), xb.data()};
   size_t launched = 0;
@@ -3115,11 +3022,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   auto kernel  = g.weighted ? k_pr_iter<V, E, R, true> : k_pr_iter<V, E, R, false>;
   pr_state* hpin = h.pinned_as<pr_state>();
   while (true) {
-    if (h.profiling) {
-      ev.push_back(h.event(ev.size()));  // pooled on the handle
-      ev.push_back(h.event(ev.size()));
-      HIP_CHECK(hipEventRecord(ev[ev.size() - 2], s));
-    }
+    timer.begin();
     int const chunk = launched == 0 && hint > 0 ? std::min(std::min(hint, 64), std::max(1, a.max_iter))
                                                 : next_chunk(hst, eps, a.max_iter);
     for (int i = 0; i < chunk; ++i) {
@@ -3138,13 +3041,12 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
       CGX_LAUNCH_CHECK();
       ++launched;
     }
-    if (h.profiling) HIP_CHECK(hipEventRecord(ev.back(), s));
+    timer.end();
     HIP_CHECK(hipMemcpyAsync(hpin, st.data(), sizeof(pr_state), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     hst = *hpin;
-    if (calibrating) {  // re-deal the queues by the recorded costs (the stream is idle here)
-      calibrate_queues(s, adj.pr, h.tune);
-      for (int q = 0; q <= kQueues; ++q) sa.qoff[q] = adj.pr.qoff[q];
+    if (calibrating) {  // (the stream is idle here)
+      redeal_queues(s, adj.pr, h.tune, sa);
       calibrating = false;
     }
     if (hst.done) break;
@@ -3177,16 +3079,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
       std::fclose(f);
     }
   }
-  if (h.profiling) {
-    double tot = 0;
-    for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      tot += ms;
-    }
-    h.last_hot_ms       = tot;
-    h.last_hot_launches = std::max<size_t>((size_t)hst.iter, 1);
-  }
+  timer.report(hst.iter);
   if (hst.done == 2) fail(CUGRAPH_UNKNOWN_ERROR, "PageRank failed to converge.");
 }
 
@@ -3373,8 +3266,7 @@ mg_pr_block& mg_block(handle_t& h, graph_t& g)
   }
   ctx.row->reduce_scatter<double>(part.data(), own.data(), (size_t)blk->nmax_row, CGX_COMM_SUM, s);
   int64_t n_own = mg.n_own();
-  blk->outw.set_stream(s);
-  blk->outw.resize(std::max<int64_t>(n_own, 1) * sizeof(R));
+  blk->outw.resize(std::max<int64_t>(n_own, 1) * sizeof(R), s);
   if (n_own)
     hipLaunchKernelGGL(k_to_weight<R>, dim3(grid_for(n_own, kBlock, 4096)), dim3(kBlock), 0, s, own.data(), n_own,
                        blk->outw.data<R>());
@@ -3477,8 +3369,7 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
   hipStream_t s   = h.stream;
   mg_context& ctx = *h.mg;
   mg_graph_t& mg  = *g.mg;
-  CGX_INPUT(alpha >= 0.0 && alpha <= 1.0, "Invalid input argument: alpha should be in [0.0, 1.0].");
-  CGX_INPUT(eps >= 0.0, "Invalid input argument: epsilon should be non-negative.");
+  check_alpha_eps(alpha, eps);
   int64_t const n_own = mg.n_own();
   res.vertices        = std::make_unique<device_array_t>((size_t)n_own, g.vertex_type, s);
   if (n_own)
@@ -3608,15 +3499,7 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
       nblk_push[k] -= kCommCUs * (pp.win_bits >= 14 ? 1 : 2);  // (blocks per CU)
     pker[k]         = push_kernel<V, E, R>(pp, g.weighted, a.enc != 0);
     // measured-cost queues (calibrate_queues), per rank and chunk: no collective
-    calibrating[k] = nblk_push[k] && calibration_wanted(pp, h.tune);
-    if (calibrating[k]) {
-      pp.item_ticks.set_stream(s);
-      pp.item_ticks.resize(pp.nitems * sizeof(uint32_t));
-      HIP_CHECK(hipMemsetAsync(pp.item_ticks.data(), 0, pp.nitems * sizeof(uint32_t), s));
-      pp.calib = 1;
-    } else if (pp.calib == 0) {
-      pp.calib = 2;
-    }
+    calibrating[k] = arm_calibration(pp, h.tune, s);  // (wanted only with items, and items mean blocks)
   }
   push_args<V, E, R> sap = spk[0];
   sap.acc       = col_reduce ? acc_own.data() : spk[0].acc;
@@ -3631,18 +3514,13 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
   }
 
   size_t launched = 0;
-  std::vector<hipEvent_t> ev;
+  chunk_timer timer{h, s, {}};
   pr_state hst{};
   pr_state* hpin = h.pinned_as<pr_state>();
   {
-    // (collectives run even in the no-op iterations after convergence: next_chunk;
-    // one pair of pooled events per chunk, as on one GPU)
+    // (collectives run even in the no-op iterations after convergence: next_chunk)
     while (true) {
-      if (h.profiling) {
-        ev.push_back(h.event(ev.size()));
-        ev.push_back(h.event(ev.size()));
-        HIP_CHECK(hipEventRecord(ev[ev.size() - 2], s));
-      }
+      timer.begin();
       int const chunk = next_chunk(hst, eps, a.max_iter);
       for (int i = 0; i < chunk; ++i) {
         ctx.row->allgather<R>(x_send.data(), x_row.data(), (size_t)blk.nmax_row, s);
@@ -3681,30 +3559,20 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
         hipLaunchKernelGGL((k_mg_finish_guarded<V, E, R>), dim3(1), dim3(64), 0, s, a, true);
         CGX_LAUNCH_CHECK();
       }
-      if (h.profiling) HIP_CHECK(hipEventRecord(ev.back(), s));
+      timer.end();
       HIP_CHECK(hipMemcpyAsync(hpin, st.data(), sizeof(pr_state), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       hst = *hpin;
       for (int k = 0; k < K; ++k) {
         if (!calibrating[k]) continue;
-        calibrate_queues(s, blk.ch[k].pp, h.tune);
-        for (int q = 0; q <= kQueues; ++q) spk[k].qoff[q] = blk.ch[k].pp.qoff[q];
+        redeal_queues(s, blk.ch[k].pp, h.tune, spk[k]);
         calibrating[k] = 0;
       }
       if (hst.done) break;
     }
   }
   h.last_iterations = (size_t)hst.iter;
-  if (h.profiling) {
-    double tot = 0;
-    for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      tot += ms;
-    }
-    h.last_hot_ms       = tot;
-    h.last_hot_launches = std::max<size_t>((size_t)hst.iter, 1);
-  }
+  timer.report(hst.iter);
   if (hst.done == 2) fail(CUGRAPH_UNKNOWN_ERROR, "PageRank failed to converge.");
 }
 
