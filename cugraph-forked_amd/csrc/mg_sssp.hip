@@ -23,12 +23,19 @@
 // fp32 relaxation is monotone, so the fixed point -- the distances -- does not
 // depend on the order of relaxations: they equal the single-GPU result bit for bit.
 // Predecessors: the distances are allgathered once, every rank offers its tight
-// out-edges (dist[u] + w == dist[v]) and the owner keeps the smallest global u.
+// out-edges from strictly closer vertices (dist[u] + w == dist[v], dist[u] <
+// dist[v]) and the owner keeps the smallest global u.  Reached vertices left without
+// one (all their tight in-neighbours are at their own distance: zero or absorbed
+// weights) are counted over all ranks, and only if there are any, level passes as in
+// sssp.hip resolve them: the ranks are allgathered, every rank offers its tight
+// equal-distance out-edges from vertices of rank k - 1 to open vertices, the owner
+// keeps the smallest global u and gives the vertex rank k.
 #include "capi.hpp"
 #include "comm.hpp"
 #include "mg_graph.hpp"
 #include "mg_route.hpp"
 #include "prims.hpp"
+#include "sssp_threshold.hpp"
 
 #include <rocprim/device/device_reduce_by_key.hpp>
 
@@ -204,7 +211,8 @@ __global__ void k_far_min(uint32_t const* far, int64_t n, W const* dist, W const
   }
 }
 
-// tight out-edges (dist[u] + w == dist[v]) -> key (v << 32 | global u)
+// tight out-edges from strictly closer vertices (dist[u] + w == dist[v], dist[u] <
+// dist[v]) -> key (v << 32 | global u)
 template <typename W>
 __global__ void k_tight(int64_t n_own, int64_t const* off, uint32_t const* idx, W const* wgt, W const* dist_all,
                         int64_t lo, uint32_t src, unsigned long long* out)
@@ -214,9 +222,44 @@ __global__ void k_tight(int64_t n_own, int64_t const* off, uint32_t const* idx, 
     W const du = dist_all[lo + u];
     for (int64_t e = off[u]; e < off[u + 1]; ++e) {
       uint32_t v = idx[e];
-      bool tight = du != BIG && v != src && du + wgt[e] == dist_all[v];
+      W const dv = dist_all[v];
+      bool tight = du != BIG && v != src && du < dv && du + wgt[e] == dv;
       out[e]     = tight ? (((unsigned long long)v << 32) | (unsigned long long)(uint32_t)(lo + u)) : ~0ull;
     }
+  }
+}
+
+// level pass `level`: tight equal-distance out-edges from vertices of rank level - 1
+// to open vertices (rank -1) -> key (v << 32 | global u)
+template <typename W>
+__global__ void k_tight_level(int64_t n_own, int64_t const* off, uint32_t const* idx, W const* wgt, W const* dist_all,
+                              int const* rank_all, int level, int64_t lo, unsigned long long* out)
+{
+  W const BIG = std::numeric_limits<W>::max();
+  for (int64_t u = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; u < n_own; u += (int64_t)gridDim.x * blockDim.x) {
+    W const du    = dist_all[lo + u];
+    bool const on = du != BIG && rank_all[lo + u] == level - 1;
+    for (int64_t e = off[u]; e < off[u + 1]; ++e) {
+      uint32_t v = idx[e];
+      bool tight = on && rank_all[v] < 0 && dist_all[v] == du && du + wgt[e] == du;
+      out[e]     = tight ? (((unsigned long long)v << 32) | (unsigned long long)(uint32_t)(lo + u)) : ~0ull;
+    }
+  }
+}
+
+// the own vertices' ranks after predecessors were set: a vertex without a rank that
+// has one now gets `level` (level 0: the source too); reached vertices still without
+// are counted
+template <typename V, typename W>
+__global__ void k_pred_ranks(V const* pred, W const* dist, int64_t n_own, int64_t src_local, int level, int* rank,
+                             unsigned long long* nopen)
+{
+  W const BIG = std::numeric_limits<W>::max();
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_own; i += (int64_t)gridDim.x * blockDim.x) {
+    int r = level == 0 ? -1 : rank[i];
+    if (r < 0 && (pred[i] != std::numeric_limits<V>::max() || (level == 0 && i == src_local))) r = level;
+    rank[i] = r;
+    if (r < 0 && dist[i] != BIG) atomicAdd(nopen, 1ull);
   }
 }
 
@@ -339,7 +382,11 @@ void mg_sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool wa
       comm.allreduce<W>(fm.data(), fm.data(), 1, CGX_COMM_MIN, s);
       W const mn = to_host_scalar(fm.data(), s);
       if (!(mn < BIG)) break;  // nothing left anywhere
-      thr = std::max<W>(thr + delta, mn + delta);
+      // mn + delta (mn >= thr: the far pile holds distances at or past it), and past
+      // mn where rounding absorbs delta: the split moves at least the vertices at mn
+      W const up = next_threshold(std::max<W>(thr, mn), delta, mn);
+      CGX_EXPECTS(up > thr, CUGRAPH_UNKNOWN_ERROR, "MG SSSP: the threshold did not advance");
+      thr = up;
       HIP_CHECK(hipMemsetAsync(cnt.data(), 0, 4 * sizeof(unsigned long long), s));
       if (n_far)
         hipLaunchKernelGGL(k_split<W>, dim3(blocks(n_far)), dim3(kBlock), 0, s, farA.data(), n_far, dist,
@@ -414,39 +461,79 @@ void mg_sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool wa
     // every rank needs dist[v] of its edges' destinations: one allgather
     int64_t nmax = 0;
     for (int q = 0; q < P; ++q) nmax = std::max(nmax, mg.voff[q + 1] - mg.voff[q]);
-    dbuf<W> sb(std::max<int64_t>(nmax, 1), s), rb(std::max<int64_t>(nmax, 1) * P, s),
-      dall(std::max<int64_t>(g.num_vertices, 1), s);
-    if (n_own) HIP_CHECK(hipMemcpyAsync(sb.data(), dist, n_own * sizeof(W), hipMemcpyDeviceToDevice, s));
-    comm.allgather<W>(sb.data(), rb.data(), (size_t)std::max<int64_t>(nmax, 1), s);
-    for (int q = 0; q < P; ++q) {
-      int64_t nq = mg.voff[q + 1] - mg.voff[q];
-      if (nq)
-        HIP_CHECK(hipMemcpyAsync(dall.data() + mg.voff[q], rb.data() + (size_t)q * std::max<int64_t>(nmax, 1),
-                                 nq * sizeof(W), hipMemcpyDeviceToDevice, s));
-    }
+    size_t const nm = (size_t)std::max<int64_t>(nmax, 1);
+    auto gather_own = [&](auto const* own, auto* all) {  // the ranks' own slices -> global id order
+      using T = std::remove_pointer_t<decltype(all)>;
+      dbuf<T> sb(nm, s), rb(nm * P, s);
+      if (n_own) HIP_CHECK(hipMemcpyAsync(sb.data(), own, n_own * sizeof(T), hipMemcpyDeviceToDevice, s));
+      comm.allgather<T>(sb.data(), rb.data(), nm, s);
+      for (int q = 0; q < P; ++q) {
+        int64_t nq = mg.voff[q + 1] - mg.voff[q];
+        if (nq)
+          HIP_CHECK(hipMemcpyAsync(all + mg.voff[q], rb.data() + (size_t)q * nm, nq * sizeof(T),
+                                   hipMemcpyDeviceToDevice, s));
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+    };
+    dbuf<W> dall(std::max<int64_t>(g.num_vertices, 1), s);
+    gather_own(dist, dall.data());
     int64_t const e1 = std::max<int64_t>(ne_own, 1);
     dbuf<unsigned long long> tk(e1, s), tk2(e1, s), tu(e1, s);
-    int64_t nt = 0;
+    // the offers in tk (one key per own out-edge, ~0: none): the smallest u per v to v's owner
+    auto offer = [&]() {
+      int64_t nt = 0;
+      if (ne_own) {
+        radix_sort_keys<unsigned long long>(tk.data(), tk2.data(), ne_own, 0, 64, s);
+        dbuf<size_t> c1(1, s);
+        size_t tmp = 0;
+        HIP_CHECK(rocprim::unique(nullptr, tmp, tk2.data(), tu.data(), c1.data(), (size_t)ne_own, same_hi(), s));
+        buffer t(tmp, s);
+        HIP_CHECK(rocprim::unique(t.data(), tmp, tk2.data(), tu.data(), c1.data(), (size_t)ne_own, same_hi(), s));
+        nt = (int64_t)to_host_scalar(c1.data(), s);
+      }
+      std::vector<size_t> counts(P, 0);
+      if (nt) counts = rank_counts(key_of<unsigned long long>{tu.data()}, nt, target_voff{voff_d.data(), 32}, P, s);
+      std::vector<size_t> rc;
+      auto got = exchange<int64_t>(comm, reinterpret_cast<int64_t const*>(tu.data()), counts, rc, s);
+      if (got.n)
+        hipLaunchKernelGGL(k_set_pred<V>, dim3(blocks(got.n)), dim3(kBlock), 0, s,
+                           reinterpret_cast<unsigned long long const*>(got.data()), (int64_t)got.n, lo, pred);
+      CGX_LAUNCH_CHECK();
+      HIP_CHECK(hipStreamSynchronize(s));
+    };
     if (ne_own) {
       hipLaunchKernelGGL(k_tight<W>, dim3(blocks(n_own)), dim3(kBlock), 0, s, n_own, rows.off.data(), rows.idx.data(),
                          rows.w.data(), dall.data(), lo, (uint32_t)src, tk.data());
       CGX_LAUNCH_CHECK();
-      radix_sort_keys<unsigned long long>(tk.data(), tk2.data(), ne_own, 0, 64, s);
-      dbuf<size_t> c1(1, s);
-      size_t tmp = 0;
-      HIP_CHECK(rocprim::unique(nullptr, tmp, tk2.data(), tu.data(), c1.data(), (size_t)ne_own, same_hi(), s));
-      buffer t(tmp, s);
-      HIP_CHECK(rocprim::unique(t.data(), tmp, tk2.data(), tu.data(), c1.data(), (size_t)ne_own, same_hi(), s));
-      nt = (int64_t)to_host_scalar(c1.data(), s);
     }
-    std::vector<size_t> counts(P, 0);
-    if (nt) counts = rank_counts(key_of<unsigned long long>{tu.data()}, nt, target_voff{voff_d.data(), 32}, P, s);
-    std::vector<size_t> rc;
-    auto got = exchange<int64_t>(comm, reinterpret_cast<int64_t const*>(tu.data()), counts, rc, s);
-    if (got.n)
-      hipLaunchKernelGGL(k_set_pred<V>, dim3(blocks(got.n)), dim3(kBlock), 0, s,
-                         reinterpret_cast<unsigned long long const*>(got.data()), (int64_t)got.n, lo, pred);
-    CGX_LAUNCH_CHECK();
+    offer();
+    // reached vertices without a predecessor (tight in-neighbours at their own distance only)
+    dbuf<int> rank(n1, s);
+    dbuf<unsigned long long> nopen(1, s);
+    auto ranks_and_open = [&](int level) {
+      HIP_CHECK(hipMemsetAsync(nopen.data(), 0, sizeof(unsigned long long), s));
+      if (n_own)
+        hipLaunchKernelGGL((k_pred_ranks<V, W>), dim3(blocks(n_own)), dim3(kBlock), 0, s, pred, dist, n_own, src - lo,
+                           level, rank.data(), nopen.data());
+      CGX_LAUNCH_CHECK();
+      return comm.host_allreduce<int64_t>((int64_t)to_host_scalar(nopen.data(), s), CGX_COMM_SUM, s);
+    };
+    int64_t open = ranks_and_open(0);
+    if (open) {
+      dbuf<int> rall(std::max<int64_t>(g.num_vertices, 1), s);
+      for (int level = 1; open; ++level) {
+        gather_own(rank.data(), rall.data());
+        if (ne_own) {
+          hipLaunchKernelGGL(k_tight_level<W>, dim3(blocks(n_own)), dim3(kBlock), 0, s, n_own, rows.off.data(),
+                             rows.idx.data(), rows.w.data(), dall.data(), rall.data(), level, lo, tk.data());
+          CGX_LAUNCH_CHECK();
+        }
+        offer();
+        int64_t const left = ranks_and_open(level);
+        CGX_EXPECTS(left < open, CUGRAPH_UNKNOWN_ERROR, "MG SSSP: a predecessor level pass resolved no vertex");
+        open = left;
+      }
+    }
     if (n_own) hipLaunchKernelGGL(k_pred_none<V>, dim3(blocks(n_own)), dim3(kBlock), 0, s, pred, n_own);
     CGX_LAUNCH_CHECK();
     mg_global_to_ext(h, g, pred, (size_t)n_own);

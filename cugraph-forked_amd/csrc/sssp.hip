@@ -53,9 +53,18 @@
 // the adjacency is built once per graph and delta (adjacency_t::sssp_*).
 // Predecessors are resolved once at the end by a pull over the in-edges (sorted
 // ascending): the first -- smallest-id -- in-neighbour u with dist[u] + w == dist[v]
-// (deterministic; every reference golden vector satisfies it).
+// and dist[u] < dist[v] (deterministic; every reference golden vector satisfies it).
+// A reached vertex without one (a zero weight, or a weight that rounding absorbs:
+// all its tight in-neighbours are at its own distance, and two such vertices are
+// tight for each other) is counted, and only if there are any, level passes resolve
+// them: pass k gives the open vertices with a tight equal-distance in-neighbour of
+// rank k - 1 (rank 0: the source and everything resolved above) the smallest such id
+// and rank k.  Ranks fall along predecessors at one distance, so the predecessors
+// always form a tree (the reference records one on a strict improvement only); a
+// graph without such vertices pays one scalar read.
 #include "capi.hpp"
 #include "prims.hpp"
+#include "sssp_threshold.hpp"
 
 #include <cfloat>
 #include <cstdio>
@@ -482,10 +491,8 @@ __global__ void k_sssp_ctl(sssp_state<W>* st, int round, int eb)
       U const mb  = st->minfar;
       W const mf  = *reinterpret_cast<W const*>(&mb);
       W const old = st->thr;
-      W thr       = old + st->delta;
-      if (!(mf < thr)) thr = mf + st->delta;
-      st->old    = old;
-      st->thr    = thr;
+      st->old     = old;
+      st->thr     = next_threshold(old, st->delta, mf);
       st->fs     = 1;
       st->minfar = inf;  // k_far_split notes the far set's exact minimum past the new thr
       st->epoch += 1;
@@ -763,17 +770,21 @@ __global__ void k_chunk_rows(E const* off, int64_t nv, int64_t* crow)
 }
 
 // Predecessors by a pull over the in-edges (sorted ascending): the first -- the
-// smallest-id -- in-neighbour u with dist[u] + w == dist[v]; -1 for the source and
-// unreached vertices.  k_sssp_pred_probe: a lane per vertex tests its first 4
-// in-edges with every load issued at once (ids descend by degree, so a vertex's
-// first neighbours are its hubs, usually the tight ones) and marks the rest kMiss;
-// k_sssp_pred_scan: a 16-lane group per marked vertex walks the list from the 5th
-// edge on, 16 at a time.
+// smallest-id -- in-neighbour u with dist[u] + w == dist[v] and dist[u] < dist[v];
+// -1 for the source and unreached vertices.  k_sssp_pred_probe: a lane per vertex
+// tests its first 4 in-edges with every load issued at once (ids descend by degree,
+// so a vertex's first neighbours are its hubs, usually the tight ones) and marks the
+// rest kPredScan; k_sssp_pred_scan: a 16-lane group per marked vertex walks the list
+// from the 5th edge on, 16 at a time.  A reached vertex neither finds a predecessor
+// for is marked kPredOpen and counted in *nopen (k_sssp_pred_level resolves those).
 constexpr int kPredProbe = 4;
+constexpr int kPredScan  = -2;
+constexpr int kPredOpen  = -3;
 
 template <typename V, typename E, typename W>
 __global__ __launch_bounds__(256) void k_sssp_pred_probe(E const* off, V const* idx, W const* wgt, W const* dist,
-                                                         int64_t nv, V const* src, V* pred)
+                                                         int64_t nv, V const* src, V* pred,
+                                                         unsigned long long* nopen)
 {
   V const s_  = *src;
   W const BIG = std::numeric_limits<W>::max();
@@ -799,30 +810,35 @@ __global__ __launch_bounds__(256) void k_sssp_pred_probe(E const* off, V const* 
     V found = V(-1);
 #pragma unroll
     for (int k = kPredProbe - 1; k >= 0; --k)
-      if (u[k] >= 0 && (W)(du[k] + w[k]) == dv) found = u[k];
-    pred[v] = want && found < 0 && end - beg > kPredProbe ? V(-2) : found;
+      if (u[k] >= 0 && du[k] < dv && (W)(du[k] + w[k]) == dv) found = u[k];
+    if (want && found < 0) {
+      found = end - beg > kPredProbe ? V(kPredScan) : V(kPredOpen);
+      if (found == V(kPredOpen)) atomicAdd(nopen, 1ull);
+    }
+    pred[v] = found;
   }
 }
 
 template <typename V, typename E, typename W>
 __global__ __launch_bounds__(256) void k_sssp_pred_scan(E const* off, V const* idx, W const* wgt, W const* dist,
-                                                        int64_t nv, V* pred)
+                                                        int64_t nv, V* pred, unsigned long long* nopen)
 {
   int const lane = threadIdx.x & 15;
   int const gsh  = threadIdx.x & 48;  // the group's first lane within the wave
   for (int64_t v0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 4; v0 < nv;
        v0 += ((int64_t)gridDim.x * blockDim.x) >> 4) {
-    if (pred[v0] != V(-2)) continue;
+    if (pred[v0] != V(kPredScan)) continue;
     W const dv  = dist[v0];
     E const beg = off[v0] + kPredProbe, end = off[v0 + 1];
-    V found     = V(-1);
+    V found     = V(kPredOpen);
     for (E base = beg; base < end; base += 16) {
       E const e  = base + lane;
       bool tight = false;
       V u        = 0;
       if (e < end) {
-        u     = idx[e];
-        tight = (W)(dist[u] + wgt[e]) == dv;
+        u          = idx[e];
+        W const du = dist[u];
+        tight      = du < dv && (W)(du + wgt[e]) == dv;
       }
       unsigned long long const m = (__ballot(tight) >> gsh) & 0xffffull;
       if (m) {
@@ -830,7 +846,75 @@ __global__ __launch_bounds__(256) void k_sssp_pred_scan(E const* off, V const* i
         break;
       }
     }
-    if (lane == 0) pred[v0] = found;
+    if (lane == 0) {
+      pred[v0] = found;
+      if (found == V(kPredOpen)) atomicAdd(nopen, 1ull);
+    }
+  }
+}
+
+// The ranks before the first level pass: 0 for the source and every vertex with a
+// predecessor, -1 for the rest; the open vertices listed (n_open of them, counted by
+// the two kernels above; *nlist starts at 0).
+template <typename V>
+__global__ void k_sssp_pred_rank0(V const* pred, int64_t nv, V const* src, int* rank, V* list,
+                                  unsigned long long* nlist)
+{
+  V const s_ = *src;
+  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nv; v += (int64_t)gridDim.x * blockDim.x) {
+    V const p = pred[v];
+    rank[v]   = ((V)v == s_ || p >= 0) ? 0 : -1;
+    if (p == V(kPredOpen)) list[atomicAdd(nlist, 1ull)] = (V)v;
+  }
+}
+
+// Level pass `level` (1, 2, ...): a block per listed vertex v that is still open
+// walks its in-edges, 256 at a time, for the first u with dist[u] == dist[v],
+// dist[u] + w == dist[v] and rank[u] == level - 1, and takes it with rank `level`; the
+// vertices still open are counted.  Only ranks below `level` match, and those were
+// fixed by earlier passes (a rank written by this pass is `level`, an open vertex's is
+// -1), so the result does not depend on the order of the list or of the blocks.  (A
+// block, not a 16-lane group: the list is short and may hold a hub, whose whole row
+// is walked.)
+template <typename V, typename E, typename W>
+__global__ __launch_bounds__(256) void k_sssp_pred_level(E const* off, V const* idx, W const* wgt, W const* dist,
+                                                         V const* list, int64_t nlist, int* rank, int level, V* pred,
+                                                         unsigned long long* nopen)
+{
+  __shared__ int s_first[4];  // per wave: its first hit's position in the 256 edges, -1 for none
+  int const tid = threadIdx.x, wv = tid >> 6;
+  for (int64_t i = blockIdx.x; i < nlist; i += gridDim.x) {
+    int64_t const v0 = (int64_t)list[i];
+    if (pred[v0] != V(kPredOpen)) continue;  // (written by this block's thread 0 only: the same for every thread)
+    W const dv  = dist[v0];
+    E const end = off[v0 + 1];
+    V found     = V(kPredOpen);
+    for (E base = off[v0]; base < end; base += 256) {
+      E const e = base + tid;
+      bool hit  = false;
+      if (e < end) {
+        V const u = idx[e];
+        hit       = dist[u] == dv && (W)(dv + wgt[e]) == dv && rank[u] == level - 1;
+      }
+      unsigned long long const m = __ballot(hit);
+      if ((tid & 63) == 0) s_first[wv] = m ? wv * 64 + __ffsll((long long)m) - 1 : -1;
+      __syncthreads();
+      int first = -1;
+      for (int w = 3; w >= 0; --w) first = s_first[w] >= 0 ? s_first[w] : first;
+      __syncthreads();
+      if (first >= 0) {
+        found = idx[base + first];
+        break;
+      }
+    }
+    if (tid == 0) {
+      if (found != V(kPredOpen)) {
+        pred[v0] = found;
+        rank[v0] = level;
+      } else {
+        atomicAdd(nopen, 1ull);
+      }
+    }
   }
 }
 
@@ -997,6 +1081,11 @@ void sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool want_
   CGX_LAUNCH_CHECK();
   auto* hs_st = h.pinned_as<sssp_state<W>>();
   int round   = 0;
+  // what the last read of the state showed: every round relaxes a list (rounds
+  // grows) or raises thr (next_threshold: strictly), so a chunk that changes none
+  // of the three would repeat for ever -- an error, not a loop
+  W seen_thr                    = W(-1);
+  unsigned long long seen_rounds = ~0ull, seen_minfar = ~0ull;
   while (true) {
     for (int k = 0; k < kChunkRounds; ++k, ++round) {
       hipLaunchKernelGGL((k_relax<V, E, W>), dim3(kRelaxGrid), dim3(256), 0, s, a, round);
@@ -1010,6 +1099,13 @@ void sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool want_
     HIP_CHECK(hipStreamSynchronize(s));
     CGX_INPUT(!hs_st->bad, "Invalid input argument: source vertex out-of-range.");
     if (hs_st->done) break;
+    CGX_EXPECTS(!(hs_st->thr == seen_thr && hs_st->rounds == seen_rounds &&
+                  (unsigned long long)hs_st->minfar == seen_minfar),
+                CUGRAPH_UNKNOWN_ERROR,
+                "SSSP: no progress in a chunk of rounds (threshold, rounds and far minimum unchanged)");
+    seen_thr    = hs_st->thr;
+    seen_rounds = hs_st->rounds;
+    seen_minfar = (unsigned long long)hs_st->minfar;
   }
   h.last_iterations = (size_t)hs_st->rounds;
   if (trace) {
@@ -1031,13 +1127,38 @@ void sssp_impl(handle_t& h, graph_t& g, size_t source, double cutoff, bool want_
   }
   if (want_pred) {
     V* pred = res.predecessors->buf.data<V>();
+    dbuf<unsigned long long> nopen(1, s);
+    HIP_CHECK(hipMemsetAsync(nopen.data(), 0, sizeof(unsigned long long), s));
     // in-edges: a symmetric graph's own rows, else the cached CSC
     adjacency_t& in = g.symmetric ? adj : ensure_adjacency(h, g, true);
     hipLaunchKernelGGL((k_sssp_pred_probe<V, E, W>), dim3(grid_for((size_t)nv, 256, 8192)), dim3(256), 0, s,
-                       in.offsets.data<E>(), in.indices.data<V>(), in.weights.data<W>(), dist, nv, src_id.data(), pred);
+                       in.offsets.data<E>(), in.indices.data<V>(), in.weights.data<W>(), dist, nv, src_id.data(), pred,
+                       nopen.data());
     hipLaunchKernelGGL((k_sssp_pred_scan<V, E, W>), dim3(grid_for((size_t)nv * 16, 256, 16384)), dim3(256), 0, s,
-                       in.offsets.data<E>(), in.indices.data<V>(), in.weights.data<W>(), dist, nv, pred);
+                       in.offsets.data<E>(), in.indices.data<V>(), in.weights.data<W>(), dist, nv, pred, nopen.data());
     CGX_LAUNCH_CHECK();
+    // vertices whose tight in-neighbours are all at their own distance: level passes
+    unsigned long long open = to_host_scalar(nopen.data(), s);
+    if (open) {
+      int64_t const nlist = (int64_t)open;
+      dbuf<int> rank(nv, s);
+      dbuf<V> list(nlist, s);
+      HIP_CHECK(hipMemsetAsync(nopen.data(), 0, sizeof(unsigned long long), s));
+      hipLaunchKernelGGL(k_sssp_pred_rank0<V>, dim3(grid_for((size_t)nv, kBlock, 8192)), dim3(kBlock), 0, s, pred, nv,
+                         src_id.data(), rank.data(), list.data(), nopen.data());
+      CGX_LAUNCH_CHECK();
+      for (int level = 1; open; ++level) {
+        HIP_CHECK(hipMemsetAsync(nopen.data(), 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL((k_sssp_pred_level<V, E, W>), dim3((unsigned)std::min<int64_t>(nlist, 16384)), dim3(256),
+                           0, s, in.offsets.data<E>(), in.indices.data<V>(), in.weights.data<W>(), dist, list.data(),
+                           nlist, rank.data(), level, pred, nopen.data());
+        CGX_LAUNCH_CHECK();
+        unsigned long long const left = to_host_scalar(nopen.data(), s);
+        // (the edge that last set dist[v] came from a vertex that is closer or was final earlier)
+        CGX_EXPECTS(left < open, CUGRAPH_UNKNOWN_ERROR, "SSSP: a predecessor level pass resolved no vertex");
+        open = left;
+      }
+    }
     unrenumber_int_to_ext(h, g, pred, (size_t)nv);
   }
 }

@@ -23,7 +23,10 @@
  *  monotone, so both reach the same fixed point: the minimum over paths of the
  *  left-folded weight_t sums below the cutoff.
  *  Predecessors: the build's deterministic rule (oracle/sssp.py): the smallest
- *  internal id among the tight in-neighbours (dist[u] + w == dist[v]); -1 when
+ *  internal id among the tight in-neighbours (dist[u] + w == dist[v]) that are
+ *  strictly closer; a vertex without one takes the smallest id among its tight
+ *  equal-distance in-neighbours of the smallest rank, level by level (rank 0: the
+ *  source and the vertices above), so the predecessors form a tree; -1 when
  *  unreached or the source.
  *
  * Returns the number of relaxation rounds; *seconds = the traversal's time
@@ -132,14 +135,39 @@
       if (ncur == 0 && nfar == 0) break;                                                                          \
     }                                                                                                             \
     *seconds = omp_get_wtime() - t0;                                                                              \
+    for (int64_t v = 0; v < nv; ++v) stamp[v] = -1; /* from here: the predecessor rank of v */                    \
+    stamp[source] = 0;                                                                                            \
     for (int64_t u = 0; u < nv; ++u) {                                                                            \
       W const du = dist[u];                                                                                       \
       if (du == WMAX) continue;                                                                                   \
       for (int64_t e = off[u]; e < off[u + 1]; ++e) {                                                             \
         int32_t const v = idx[e];                                                                                 \
-        if (v == source || (W)(du + wgt[e]) != dist[v]) continue;                                                 \
+        if (v == source || !(du < dist[v]) || (W)(du + wgt[e]) != dist[v]) continue;                              \
         if (pred[v] < 0 || u < pred[v]) pred[v] = (int32_t)u;                                                     \
+        stamp[v] = 0;                                                                                             \
       }                                                                                                           \
+    }                                                                                                             \
+    int64_t nopen = 0; /* reached vertices whose tight in-neighbours are all at their own distance */             \
+    for (int64_t v = 0; v < nv; ++v) nopen += dist[v] != WMAX && stamp[v] < 0;                                    \
+    for (int32_t lvl = 0; nopen > 0; ++lvl) {                                                                     \
+      int64_t got = 0;                                                                                            \
+      for (int64_t u = 0; u < nv; ++u) {                                                                          \
+        W const du = dist[u];                                                                                     \
+        if (du == WMAX || stamp[u] != lvl) continue;                                                              \
+        for (int64_t e = off[u]; e < off[u + 1]; ++e) {                                                           \
+          int32_t const v = idx[e];                                                                               \
+          if ((stamp[v] >= 0 && stamp[v] != lvl + 1) || dist[v] != du || (W)(du + wgt[e]) != du) continue;        \
+          if (stamp[v] < 0) {                                                                                     \
+            stamp[v] = lvl + 1;                                                                                   \
+            pred[v]  = (int32_t)u;                                                                                \
+            ++got;                                                                                                \
+          } else if (u < pred[v]) {                                                                               \
+            pred[v] = (int32_t)u;                                                                                 \
+          }                                                                                                       \
+        }                                                                                                         \
+      }                                                                                                           \
+      if (got == 0) break;                                                                                        \
+      nopen -= got;                                                                                               \
     }                                                                                                             \
     free(cur); free(nxt); free(far); free(far2); free(stamp);                                                     \
     return round;                                                                                                 \

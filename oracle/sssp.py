@@ -11,10 +11,17 @@ here by frontier Bellman-Ford in the same precision.
 Predecessors: the reference reduces pushes with ``reduce_op::minimum`` on the
 (distance, predecessor) tuple (``:209``, ``prims/reduce_op.cuh:68-80``), so equal
 distances pick the smaller predecessor within one push round.  Our build makes
-the choice order-independent: the smallest internal id among all tight
-in-neighbours (``dist[u] + w == dist[v]``), which matches every reference golden
-vector (``cpp/tests/c_api/sssp_test.c:182-187``,
-``python/pylibcugraph/pylibcugraph/tests/test_sssp.py``).
+the choice order-independent: the smallest internal id among the tight
+in-neighbours (``dist[u] + w == dist[v]``) that are strictly closer
+(``dist[u] < dist[v]``), which matches every reference golden vector
+(``cpp/tests/c_api/sssp_test.c:182-187``,
+``python/pylibcugraph/pylibcugraph/tests/test_sssp.py``).  A vertex without one
+(zero weights, or a weight absorbed by rounding: every tight in-neighbour is at
+its own distance) has rank k + 1, k the smallest rank among its tight
+equal-distance in-neighbours (rank 0: the source and the vertices above), and takes
+the smallest id of rank k.  The ranks strictly decrease along predecessors at one
+distance, so the predecessors always form a tree, as the reference's do (it
+records one only on a strict improvement).
 """
 from __future__ import annotations
 
@@ -55,17 +62,39 @@ def sssp(num_vertices, offsets, indices, weights, source, cutoff=np.inf, dtype=n
         before = dist.copy()
         np.minimum.at(dist, v, nd)
         frontier = np.nonzero(dist < before)[0]
-    # predecessor: min tie-key over tight in-edges
+    # predecessor: min tie-key over the tight in-edges from strictly closer vertices
+    # (rank 0); vertices left over (every tight in-edge has dist[u] == dist[v]) are
+    # resolved level by level from the tight equal-distance in-neighbours fixed by
+    # the level before
     key = np.arange(V, dtype=np.int64) if tie_key is None else np.asarray(tie_key, dtype=np.int64)
+    imax = np.iinfo(np.int64).max
     srcs = np.repeat(np.arange(V, dtype=np.int64), deg_all)
     reach = dist[srcs] < big
     s, d, ww = srcs[reach], indices[reach], w[reach]
     tight = ((dist[s] + ww).astype(dtype) == dist[d]) & (d != source)
     s, d = s[tight], d[tight]
-    best = np.full(V, np.iinfo(np.int64).max, dtype=np.int64)
-    np.minimum.at(best, d, key[s])
-    has = best != np.iinfo(np.int64).max
     inv = np.empty(V, dtype=np.int64)
     inv[key] = np.arange(V, dtype=np.int64)
+    closer = dist[s] < dist[d]
+    best = np.full(V, imax, dtype=np.int64)
+    np.minimum.at(best, d[closer], key[s[closer]])
+    has = best != imax
     pred[has] = inv[best[has]]
+    s, d = s[~closer], d[~closer]
+    rank = np.full(V, -1, dtype=np.int64)
+    rank[has] = 0
+    rank[source] = 0
+    level = 0
+    while s.size:
+        open_ = rank[d] < 0
+        s, d = s[open_], d[open_]
+        m = rank[s] == level
+        if not m.any():
+            break
+        best = np.full(V, imax, dtype=np.int64)
+        np.minimum.at(best, d[m], key[s[m]])
+        has = best != imax
+        pred[has] = inv[best[has]]
+        level += 1
+        rank[has] = level
     return dist, pred

@@ -105,6 +105,26 @@ def test_sssp_matches_oracle(scale, symmetric, wdtype, cutoff):
         assert np.array_equal(pred.astype(np.int64), rp)
 
 
+@pytest.mark.parametrize("symmetric", [True, False])
+@pytest.mark.parametrize("lo,hi", [(0, 2), (1, 3)])
+def test_sssp_integer_weights_match_oracle(lo, hi, symmetric):
+    """Integer weights lo..hi: ties at most vertices and, from 0, tight edges between
+    vertices at one distance -- the two oracles' predecessor levels stay pinned to
+    each other (tests/test_sssp_rule.py checks the numpy one)."""
+    from oracle import sssp as osssp
+    s, d = rmat.rmat(11, 16 << 11, seed=42)
+    w = np.floor(rmat.rmat_weights(s.size, seed=43).astype(np.float64) * (hi - lo + 1)) + lo
+    s, d, w = og.symmetrize_dedup(s, d, w, symmetrize=symmetric)
+    g = og.create_graph(s, d, w, renumber=True)
+    V = g.num_vertices
+    for src in (0, 1, V // 2, V - 1):
+        for wdtype in (np.float32, np.float64):
+            rd, rp = osssp.sssp(V, g.offsets, g.indices, g.weights, src, dtype=wdtype)
+            _, dist, pred, _ = cpu.sssp(g.offsets, g.indices, g.weights.astype(wdtype), src)
+            assert np.array_equal(dist, rd)
+            assert np.array_equal(pred.astype(np.int64), rp), f"source {src} {np.dtype(wdtype).name}"
+
+
 def test_sssp_c_golden(golden):
     """cpp/tests/c_api/sssp_test.c:178-230 through the compiled restatement."""
     g = golden["sssp_c"]

@@ -445,13 +445,17 @@ def test_mg_personalized_pagerank_options(world, C):
     _spawn(_pr_options_worker, (world, _free_port(), C), world)
 
 
-def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff):
+def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff, weights=None):
     """MG SSSP vs the oracle's fp32 min-plus fixed point: distances bit-identical,
     predecessors = the tight in-neighbour with the smallest global id (the oracle's
-    tie_key set to the MG global order)."""
+    tie_key set to the MG global order).  weights (lo, hi): integer weights lo..hi
+    (ties, and from 0 tight edges between vertices at one distance) from a source that
+    is not global id 0, the gathered result through tests/sssp_check.py on rank 0
+    (tight, a tree, the deterministic rule)."""
     import sys
     sys.path.insert(0, PKG)
     sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     _rank_setup(port, rank)
@@ -466,6 +470,8 @@ def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff):
 
     s, d = rmat.rmat(scale, 16 << scale, seed=11)
     w = rmat.rmat_weights(s.size, seed=43).astype(np.float64)
+    if weights is not None:
+        w = np.floor(w * (weights[1] - weights[0] + 1)) + weights[0]
     s, d, w = og.symmetrize_dedup(s, d, w, symmetrize=symmetric)
     E = s.size
     lo, hi = _slice(rank, world, E)
@@ -474,7 +480,7 @@ def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff):
     dev = lambda a, t: torch.as_tensor(np.ascontiguousarray(a).astype(t), device="cuda")  # noqa: E731
     G = plc.MGGraph(h, plc.GraphProperties(is_symmetric=symmetric, is_multigraph=False), dev(s[lo:hi], np.int32),
                     dev(d[lo:hi], np.int32), dev(w[lo:hi], np.float32), store_transposed=False, num_edges=E)
-    src = int(s[0])
+    src = int(s[0]) if weights is None else int(d[-1])
     v, dd, pp = plc.sssp(h, G, src, cutoff, True, True)
     allr = [None] * world
     dist.all_gather_object(allr, (v.cpu().numpy(), dd.cpu().numpy(), pp.cpu().numpy()))
@@ -491,6 +497,15 @@ def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff):
         rd, rp = osssp.sssp(n_ext, G2.offsets, G2.indices, G2.weights, src, cutoff=cutoff, tie_key=key)
         assert np.array_equal(dv, rd[vv])
         assert np.array_equal(pv, rp[vv])
+        if weights is not None:
+            from sssp_check import check_sssp
+            assert int(vv[0]) != src
+            fd = np.full(n_ext, np.finfo(np.float32).max, np.float32)
+            fp = np.full(n_ext, -1, np.int64)
+            fd[vv] = dv
+            fp[vv] = pv
+            rank = check_sssp(G2.offsets, G2.indices, G2.weights, src, fd, fp, cutoff, tie_key=key)
+            assert (rank.max() > 0) == (weights[0] == 0)  # zero weights: the level passes ran
     dist.barrier()
     h = None
     G = None
@@ -502,6 +517,11 @@ def _sssp_worker(rank, world, port, C, scale, symmetric, cutoff):
                                                        (4, 2, True, 0.05)])
 def test_mg_sssp_vs_oracle(world, C, symmetric, cutoff):
     _spawn(_sssp_worker, (world, _free_port(), C, 11, symmetric, float(cutoff)), world)
+
+
+@pytest.mark.parametrize("world,C,symmetric,weights", [(2, 2, True, (0, 2)), (3, 3, False, (1, 3))])
+def test_mg_sssp_integer_weights(world, C, symmetric, weights):
+    _spawn(_sssp_worker, (world, _free_port(), C, 11, symmetric, float("inf"), weights), world)
 
 
 @pytest.mark.parametrize("algo", ["pagerank", "bfs_do", "louvain", "sssp"])

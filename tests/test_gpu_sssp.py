@@ -1,5 +1,6 @@
 """SSSP parity: fp32/fp64 distances bit-identical to the oracle's min-plus fixed
-point; predecessors = smallest tight in-neighbour (golden vectors agree)."""
+point; predecessors = smallest strictly closer tight in-neighbour (golden vectors
+agree).  Ties, zero weights, chunk edges and options: tests/test_gpu_sssp_cases.py."""
 import numpy as np
 import pytest
 
@@ -8,6 +9,7 @@ from gpu_util import host, make_graph, plc
 from oracle import graph as og
 from oracle import rmat
 from oracle import sssp as osssp
+from sssp_check import pred_is_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -103,7 +105,10 @@ def test_rmat_uniform_weights_vs_compiled_oracle(scale, wdtype):
     with the bench's uniform [0, 1) weights (cugraph_funcs.py:56-58), from 4 sources
     (the largest hub, two random vertices, a low-degree vertex): distances bit-exact
     against the compiled near-far restatement (oracle/cpu_sssp.c) on the library's own
-    CSR, and every predecessor the smallest tight in-neighbour."""
+    CSR, and every predecessor the smallest strictly closer tight in-neighbour, or
+    the level rule's where there is none (the 24-bit weights include 0, and from some
+    sources an equal-distance tight in-neighbour has the smaller id: there the rule
+    before this one gave another answer); the predecessors form a tree."""
     import torch
     from oracle import cpu_native
     p = plc()
@@ -135,6 +140,8 @@ def test_rmat_uniform_weights_vs_compiled_oracle(scale, wdtype):
         assert np.array_equal(dist, rd), f"source {src_int}: distances differ from the compiled oracle"
         want = np.where(rp >= 0, nm[np.maximum(rp, 0)], -1)
         assert np.array_equal(pred.astype(np.int64), want.astype(np.int64)), f"source {src_int}: predecessors"
+        lost = pred_is_tree(rp.astype(np.int64), src_int, rd < np.finfo(wdtype).max)
+        assert lost.size == 0, f"source {src_int}: {lost.size} vertices' predecessors never get to the source"
         reached = int((rd < np.finfo(wdtype).max).sum())
         print(f"RMAT-{scale} {np.dtype(wdtype).name} SSSP from internal {src_int}: reached {reached} of {V}, "
               f"GPU rounds {h.last_iterations()}, oracle rounds {rounds} ({t:.2f} s)")
