@@ -72,6 +72,8 @@ struct tuning_t {
                                 // (wcc.hip; 0: no guess, every row fully linked)
   int tc_path          = 0;     // triangle count: 0 an oriented edge goes to a thread or a wave by its row sizes,
                                 // 1 every edge to a thread, 2 every edge to a wave (triangle_count.hip)
+  int core_scan        = 0;     // core number: 0 a level's scan reads every vertex, 1 it reads the compacted list of
+                                // the vertices not yet peeled (core_number.hip; 0 measured faster)
 };
 
 struct handle_t {
@@ -298,6 +300,17 @@ struct labeling_result_t {  // reference c_api/labeling_result.hpp
 struct triangle_count_result_t {  // reference c_api/triangle_count.cpp
   std::unique_ptr<device_array_t> vertices;
   std::unique_ptr<device_array_t> counts;  // edge type
+};
+
+struct core_result_t {  // reference c_api/core_result.hpp
+  std::unique_ptr<device_array_t> vertices;
+  std::unique_ptr<device_array_t> core_numbers;  // edge type
+};
+
+struct k_core_result_t {  // reference c_api/core_result.hpp
+  std::unique_ptr<device_array_t> src;
+  std::unique_ptr<device_array_t> dst;
+  std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
 };
 
 struct paths_result_t {

@@ -1,6 +1,6 @@
 // libcugraph_c algorithm entry points on the hot path (MI355X build):
 // PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components, triangle
-// counting and their result objects.
+// counting, core number / k-core and their result objects.
 //
 // Argument checks and error behaviour follow cpp/src/c_api/{pagerank.cpp:244-304,
 // bfs.cpp:187-230, sssp.cpp:146-190, louvain.cpp:152-190} and the result getters
@@ -32,6 +32,9 @@ void run_extract_paths(handle_t& h, graph_t& g, paths_result_t const& pr, array_
 void run_wcc(handle_t& h, graph_t& g, bool expensive, labeling_result_t& res);
 void run_triangle_count(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
                         triangle_count_result_t& res);
+void run_core_number(handle_t& h, graph_t& g, int delta, bool expensive, core_result_t& res);
+void run_k_core(handle_t& h, graph_t& g, size_t k, int delta, core_result_t const* given, bool expensive,
+                k_core_result_t& res);
 void mg_run_pagerank(handle_t& h, graph_t& g, array_view_t const* pow_v, array_view_t const* pow_s,
                      array_view_t const* guess_v, array_view_t const* guess_s, array_view_t const* pers_v,
                      array_view_t const* pers_s, double alpha, double eps, size_t max_iter, bool expensive,
@@ -328,6 +331,141 @@ extern "C" cugraph_type_erased_device_array_view_t* cugraph_triangle_count_resul
 extern "C" void cugraph_triangle_count_result_free(cugraph_triangle_count_result_t* result)
 {
   delete reinterpret_cast<triangle_count_result_t*>(result);
+}
+
+// ============================================================== core number / k-core
+// (reference c_api/core_number.cpp, c_api/k_core.cpp, c_api/core_result.cpp, cores/core_number_impl.cuh:93-106)
+namespace {
+
+// the peeling step per neighbour: 1, or 2 for INOUT (core_number_impl.cuh:110-122)
+int core_delta(cugraph_k_core_degree_type_t degree_type)
+{
+  CGX_INPUT(degree_type == K_CORE_DEGREE_TYPE_IN || degree_type == K_CORE_DEGREE_TYPE_OUT ||
+              degree_type == K_CORE_DEGREE_TYPE_INOUT,
+            "Invalid input argument: degree_type should be IN, OUT, or INOUT.");
+  return degree_type == K_CORE_DEGREE_TYPE_INOUT ? 2 : 1;
+}
+
+void core_graph_checks(graph_t const& g, char const* multi_gpu_message)
+{
+  CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED, multi_gpu_message);
+  CGX_INPUT(g.symmetric, "Invalid input argument: core_number currently supports only undirected graphs.");
+  CGX_INPUT(!g.multigraph, "Invalid input argument: core_number currently does not support multi-graphs.");
+}
+
+}  // namespace
+
+extern "C" cugraph_error_code_t cugraph_core_number(const cugraph_resource_handle_t* handle,
+                                                   cugraph_graph_t* graph,
+                                                   cugraph_k_core_degree_type_t degree_type,
+                                                   bool_t do_expensive_check,
+                                                   cugraph_core_result_t** result,
+                                                   cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    core_graph_checks(g, "multi-GPU core_number is not implemented in this build");
+    int const delta = core_delta(degree_type);
+    auto res        = std::make_unique<core_result_t>();
+    run_core_number(*H(handle), g, delta, do_expensive_check == TRUE, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_core_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_error_code_t cugraph_k_core(const cugraph_resource_handle_t* handle,
+                                              cugraph_graph_t* graph,
+                                              size_t k,
+                                              cugraph_k_core_degree_type_t degree_type,
+                                              const cugraph_core_result_t* core_result,
+                                              bool_t do_expensive_check,
+                                              cugraph_k_core_result_t** result,
+                                              cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    core_graph_checks(g, "multi-GPU k_core is not implemented in this build");
+    int const delta = core_result ? 1 : core_delta(degree_type);  // ignored with a given result
+    auto res        = std::make_unique<k_core_result_t>();
+    run_k_core(*H(handle), g, k, delta, reinterpret_cast<core_result_t const*>(core_result),
+               do_expensive_check == TRUE, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_k_core_result_t*>(res.release());
+  });
+}
+
+// c_api/core_result.cpp: both views are copied into a result of its own
+extern "C" cugraph_error_code_t cugraph_core_result_create(const cugraph_resource_handle_t* handle,
+                                                          cugraph_type_erased_device_array_view_t* vertices,
+                                                          cugraph_type_erased_device_array_view_t* core_numbers,
+                                                          cugraph_core_result_t** core_result,
+                                                          cugraph_error_t** error)
+{
+  *core_result = nullptr;
+  *error       = nullptr;
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(vertices != nullptr && core_numbers != nullptr, "Invalid input argument: a core result array is NULL");
+    hipStream_t s = H(handle)->stream;
+    auto res      = std::make_unique<core_result_t>();
+    auto copy     = [&](array_view_t const& v) {
+      auto a = std::make_unique<device_array_t>(v.size, v.type, s);
+      if (v.size) HIP_CHECK(hipMemcpyAsync(a->buf.data(), v.data, v.size * dtype_size(v.type), hipMemcpyDefault, s));
+      return a;
+    };
+    res->vertices     = copy(*AV(vertices));
+    res->core_numbers = copy(*AV(core_numbers));
+    HIP_CHECK(hipStreamSynchronize(s));
+    *core_result = reinterpret_cast<cugraph_core_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_core_result_get_vertices(cugraph_core_result_t* result)
+{
+  return new_view(reinterpret_cast<core_result_t*>(result)->vertices.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_core_result_get_core_numbers(
+  cugraph_core_result_t* result)
+{
+  return new_view(reinterpret_cast<core_result_t*>(result)->core_numbers.get());
+}
+
+extern "C" void cugraph_core_result_free(cugraph_core_result_t* result)
+{
+  delete reinterpret_cast<core_result_t*>(result);
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_k_core_result_get_src_vertices(
+  cugraph_k_core_result_t* result)
+{
+  return new_view(reinterpret_cast<k_core_result_t*>(result)->src.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_k_core_result_get_dst_vertices(
+  cugraph_k_core_result_t* result)
+{
+  return new_view(reinterpret_cast<k_core_result_t*>(result)->dst.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_k_core_result_get_weights(
+  cugraph_k_core_result_t* result)
+{
+  auto* r = reinterpret_cast<k_core_result_t*>(result);
+  return r->weights ? new_view(r->weights.get()) : nullptr;
+}
+
+extern "C" void cugraph_k_core_result_free(cugraph_k_core_result_t* result)
+{
+  delete reinterpret_cast<k_core_result_t*>(result);
 }
 
 // ============================================================== Louvain

@@ -564,6 +564,10 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: tc_path must be 0, 1 or 2");
       i32(t.tc_path);
     }
+    else if (n == "core_scan") {
+      CGX_INPUT(value == 0 || value == 1, "Invalid input argument: core_scan must be 0 or 1");
+      i32(t.core_scan);
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

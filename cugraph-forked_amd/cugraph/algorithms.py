@@ -360,6 +360,78 @@ def triangle_count(G, start_list=None):
     return df
 
 
+def core_number(G, degree_type=None):
+    """cores/core_number.py:25-101.  Returns DataFrame ['vertex', 'core_number'] (dict
+    {node: core number} for a NetworkX input): the numbers ``networkx.core_number`` gives for
+    the graph without its self-loops.  As in the reference ``degree_type`` is ignored with a
+    warning.  Undirected graphs only."""
+    import pandas as pd
+    if degree_type is not None:
+        warnings.warn("The 'degree_type' parameter is ignored in this release.", Warning)
+    if G.is_directed():
+        raise ValueError("input graph must be undirected")
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    p = _plc()
+    vertex, numbers = p.core_number(p.ResourceHandle(), G._plc_graph, None, False)
+    df = pd.DataFrame({"vertex": vertex.cpu().numpy(), "core_number": numbers.cpu().numpy()})
+    if nxv is not None:
+        return dict(zip(nxv.label(df["vertex"]), df["core_number"]))
+    return df
+
+
+def k_core(G, k=None, core_number=None):
+    """cores/k_core.py:39-129.  The k-core of G as a Graph of G's type (a NetworkX graph for a
+    NetworkX input), with G's weights if it has them.  ``k`` None: the main core.
+    ``core_number``: a precomputed DataFrame with columns 'vertex' and 'values'; None computes
+    the core numbers.  A k above the largest core number gives a graph without edges."""
+    import pandas as pd
+    import torch
+    if G.is_directed():
+        raise ValueError("G must be an undirected Graph instance")
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    out = type(G)()
+    p = _plc()
+    h = p.ResourceHandle()
+    if core_number is not None:
+        ids = _frame_col(core_number, "vertex")
+        if nxv is not None:
+            ids = torch.as_tensor(nxv.ids(list(ids.tolist())))
+        # the C entry takes the numbers in the graph's edge type (capi_core.cpp: the vertex type below 2^31 - 1 edges)
+        et = torch.int64 if G.edgelist["src"].numel() >= 2**31 - 1 else _vertex_dtype(G)
+        given = (_cuda_like(ids, _vertex_dtype(G)), _cuda_like(_frame_col(core_number, "values"), et))
+    else:
+        given = p.core_number(h, G._plc_graph, None, False)
+    if k is None:
+        k = int(given[1].max().item()) if given[1].numel() else 0
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 0:
+        raise ValueError(f"'k' must be a non-negative integer or None, got: {k}")
+    src, dst, w = p.k_core(h, G._plc_graph, int(k), None, given, False)
+    src, dst = src.cpu().numpy(), dst.cpu().numpy()
+    w = None if w is None else w.cpu().numpy()
+    if nxv is not None:
+        import networkx as nx
+        res = nx.Graph()
+        labels_s, labels_d = nxv.label(src), nxv.label(dst)
+        if w is None:
+            res.add_edges_from(zip(labels_s, labels_d))
+        else:
+            res.add_weighted_edges_from(zip(labels_s, labels_d, w.tolist()))
+        return res
+    if len(src):
+        cols = {"src": src, "dst": dst}
+        if w is not None:
+            cols["weights"] = w
+        out.from_pandas_edgelist(pd.DataFrame(cols), "src", "dst", "weights" if w is not None else None,
+                                 renumber=G._renumber, store_transposed=G.store_transposed)
+    return out
+
+
 def _max_degree(G):
     import torch
     e = G.edgelist

@@ -7,7 +7,8 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 (personalized_pagerank.pyx), ``bfs`` (bfs.pyx:59-200), ``sssp`` (sssp.pyx:52-178),
 ``louvain`` (louvain.pyx:58-149), ``weakly_connected_components``
 (weakly_connected_components.pyx, components/_connectivity.pyx:132-220), ``triangle_count``
-(triangle_count.pyx:57-60) -- same argument names, order, return tuples and
+(triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140) and ``k_core`` (the C
+entry of core_algorithms.h) -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -25,7 +26,7 @@ from . import comms  # noqa: E402,F401  (multi-GPU communicator contexts)
 __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", "MGGraph", "pagerank",
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
-           "version"]
+           "core_number", "k_core", "version"]
 
 
 def allocator_stats():
@@ -482,3 +483,64 @@ def triangle_count(resource_handle, graph, start_list, do_expensive_check):
                                                         _lib.lib.cugraph_triangle_count_result_get_counts(res)],
                                   res, _lib.lib.cugraph_triangle_count_result_free)
     return v, c
+
+
+_DEGREE_TYPES = {"incoming": 0, "outgoing": 1, "bidirectional": 2}  # cugraph_k_core_degree_type_t
+
+
+def _core_number(resource_handle, graph, degree_type_id, do_expensive_check):
+    """cugraph_core_number with the C enum value given as it is (0 in, 1 out, 2 in + out)."""
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_core_number", resource_handle.ptr, graph.c_graph_ptr, int(degree_type_id),
+              int(bool(do_expensive_check)), ctypes.byref(res))
+    v, c = views_to_tensors_owned(resource_handle.ptr, [_lib.lib.cugraph_core_result_get_vertices(res),
+                                                        _lib.lib.cugraph_core_result_get_core_numbers(res)],
+                                  res, _lib.lib.cugraph_core_result_free)
+    return v, c
+
+
+def core_number(resource_handle, graph, degree_type, do_expensive_check):
+    """core_number.pyx:58-140.  Returns (vertices, core_numbers): every vertex's core number
+    in the underlying simple graph (self-loops and repeated entries do not count), in the
+    graph's edge type; the numbers NetworkX's ``core_number`` gives.  As in the reference a
+    ``degree_type`` other than None is ignored with a warning.  The graph must be symmetric;
+    with ``do_expensive_check`` a graph that has self-loops raises ValueError."""
+    if degree_type is not None:
+        import warnings
+        warnings.warn("The 'degree_type' parameter is ignored in this release.", Warning)
+    return _core_number(resource_handle, graph, _DEGREE_TYPES["incoming"], do_expensive_check)
+
+
+def k_core(resource_handle, graph, k, degree_type, core_result, do_expensive_check):
+    """C entry cugraph_k_core (core_algorithms.h; the reference snapshot has no binding for it
+    and its C++ k_core is unimplemented).  Returns (src, dst, weights or None): the stored
+    edges, both directions, whose endpoints both have a core number of at least ``k``, without
+    self-loops and repeats.  ``core_result`` is None (the core numbers are computed inside
+    with ``degree_type``: None / "incoming" / "outgoing" the ordinary ones, "bidirectional"
+    twice those) or a pair (vertices, core_numbers) in the graph's vertex and edge types;
+    vertices it does not list count as core 0, and an id that is not in the graph is skipped,
+    or raises ValueError with ``do_expensive_check``."""
+    if degree_type is not None and degree_type not in _DEGREE_TYPES:
+        raise ValueError(f"'degree_type' must be one of {sorted(_DEGREE_TYPES)} or None, got: {degree_type}")
+    if int(k) < 0:
+        raise ValueError(f"'k' must be non-negative, got: {k}")
+    h = resource_handle.ptr
+    given = ctypes.c_void_p()
+    views = None
+    if core_result is not None:
+        vertices, numbers = core_result
+        views = (DeviceView(vertices), DeviceView(numbers))
+        _lib.call("cugraph_core_result_create", h, views[0].ptr, views[1].ptr, ctypes.byref(given))
+    res = ctypes.c_void_p()
+    try:
+        _lib.call("cugraph_k_core", h, graph.c_graph_ptr, int(k), _DEGREE_TYPES[degree_type or "incoming"], given,
+                  int(bool(do_expensive_check)), ctypes.byref(res))
+    finally:
+        if given:
+            _lib.lib.cugraph_core_result_free(given)
+    ptrs = [_lib.lib.cugraph_k_core_result_get_src_vertices(res), _lib.lib.cugraph_k_core_result_get_dst_vertices(res)]
+    w = _lib.lib.cugraph_k_core_result_get_weights(res)
+    if w:
+        ptrs.append(w)
+    out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_k_core_result_free)
+    return out[0], out[1], (out[2] if w else None)

@@ -124,6 +124,16 @@ _proto("cugraph_triangle_count", c_int, P, P, P, c_int, PP, PP)
 _proto("cugraph_triangle_count_result_get_vertices", P, P)
 _proto("cugraph_triangle_count_result_get_counts", P, P)
 _proto("cugraph_triangle_count_result_free", None, P)
+_proto("cugraph_core_number", c_int, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_k_core", c_int, P, P, c_size_t, c_int, P, c_int, PP, PP)
+_proto("cugraph_core_result_create", c_int, P, P, P, PP, PP)
+_proto("cugraph_core_result_get_vertices", P, P)
+_proto("cugraph_core_result_get_core_numbers", P, P)
+_proto("cugraph_core_result_free", None, P)
+_proto("cugraph_k_core_result_get_src_vertices", P, P)
+_proto("cugraph_k_core_result_get_dst_vertices", P, P)
+_proto("cugraph_k_core_result_get_weights", P, P)
+_proto("cugraph_k_core_result_free", None, P)
 _proto("cugraph_louvain", c_int, P, P, c_size_t, c_double, c_int, PP, PP)
 _proto("cugraph_heirarchical_clustering_result_get_vertices", P, P)
 _proto("cugraph_heirarchical_clustering_result_get_clusters", P, P)

@@ -126,7 +126,8 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * louvain_big_maxdeg, louvain_wide_keys, sssp_delta (0 | scale: delta = scale * average weight /
  * average degree), sssp_pull (0 by size | -1 never | n), wcc_sample (neighbours linked per vertex before
  * the giant component is guessed, 0: none), tc_path (triangle count: 0 thread or wave per oriented edge by
- * row size | 1 always a thread | 2 always a wave); "defaults" resets them all.  Booleans
+ * row size | 1 always a thread | 2 always a wave), core_scan (core number: 0 the scan of a level reads every
+ * vertex | 1 it reads the compacted list of the vertices not yet peeled); "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,

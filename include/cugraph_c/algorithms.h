@@ -6,6 +6,7 @@
 #include <cugraph_c/array.h>
 #include <cugraph_c/centrality_algorithms.h>
 #include <cugraph_c/community_algorithms.h>
+#include <cugraph_c/core_algorithms.h>
 #include <cugraph_c/error.h>
 #include <cugraph_c/graph.h>
 #include <cugraph_c/labeling_algorithms.h>
