@@ -29,7 +29,10 @@ def _pull(n, src, dst, w, x):
     return y
 
 
-def katz(num_vertices, src, dst, weights, alpha, beta, epsilon, max_iterations, betas=None, normalize=True):
+def katz(num_vertices, src, dst, weights, alpha, beta, epsilon, max_iterations, betas=None, normalize=True,
+         return_trace=False):
+    """return_trace: (values, L1 difference of every iteration) -- the iteration count
+    is the trace's length."""
     n = int(num_vertices)
     src = np.asarray(src, np.int64)
     dst = np.asarray(dst, np.int64)
@@ -37,9 +40,11 @@ def katz(num_vertices, src, dst, weights, alpha, beta, epsilon, max_iterations, 
     b = np.full(n, float(beta)) if betas is None else np.asarray(betas, np.float64)
     x = np.zeros(n)
     it = 0
+    trace = []
     while True:
         new = alpha * _pull(n, src, dst, w, x) + b
         diff = np.abs(new - x).sum()
+        trace.append(diff)
         x = new
         it += 1
         if diff < epsilon:
@@ -51,30 +56,34 @@ def katz(num_vertices, src, dst, weights, alpha, beta, epsilon, max_iterations, 
         if not nrm > 0:
             raise RuntimeError("L2 norm of the computed Katz Centrality values should be positive.")
         x = x / nrm
-    return x
+    return (x, trace) if return_trace else x
 
 
-def eigenvector_centrality(num_vertices, src, dst, weights, epsilon, max_iterations):
+def eigenvector_centrality(num_vertices, src, dst, weights, epsilon, max_iterations, return_trace=False):
+    """return_trace: (values, L1 difference of every iteration), as katz()."""
     n = int(num_vertices)
     src = np.asarray(src, np.int64)
     dst = np.asarray(dst, np.int64)
     w = np.ones(src.size) if weights is None else np.asarray(weights, np.float64)
     x = np.full(n, 1.0 / n)
     it = 0
+    trace = []
     while True:
         old = x
         y = _pull(n, src, dst, w, x)
         x = y / np.sqrt((y * y).sum())
         diff = np.abs(x - old).sum()
+        trace.append(diff)
         it += 1
         if diff < n * epsilon:
-            return x
+            return (x, trace) if return_trace else x
         if it >= max_iterations:
             raise RuntimeError("Eigenvector Centrality failed to converge.")
 
 
-def hits(num_vertices, src, dst, epsilon, max_iterations, initial_hubs=None, normalize=True):
-    """Returns (hubs, authorities, diff_sum, iterations)."""
+def hits(num_vertices, src, dst, epsilon, max_iterations, initial_hubs=None, normalize=True, return_trace=False):
+    """Returns (hubs, authorities, diff_sum, iterations); with return_trace also the
+    difference of every iteration run, as a fifth item."""
     n = int(num_vertices)
     src = np.asarray(src, np.int64)
     dst = np.asarray(dst, np.int64)
@@ -87,6 +96,7 @@ def hits(num_vertices, src, dst, epsilon, max_iterations, initial_hubs=None, nor
     diff = np.finfo(np.float64).max
     iters = max_iterations
     auth = np.zeros(n)
+    trace = []
     for it in range(max_iterations):
         auth = _pull(n, src, dst, ones, hubs)
         new = _pull(n, dst, src, ones, auth)
@@ -96,6 +106,7 @@ def hits(num_vertices, src, dst, epsilon, max_iterations, initial_hubs=None, nor
         new = new / mh
         auth = auth / ma
         diff = np.abs(new - hubs).sum()
+        trace.append(diff)
         hubs = new
         if diff < epsilon:
             iters = it
@@ -103,4 +114,4 @@ def hits(num_vertices, src, dst, epsilon, max_iterations, initial_hubs=None, nor
     if normalize:
         hubs = hubs / hubs.sum()
         auth = auth / auth.sum()
-    return hubs, auth, diff, iters
+    return (hubs, auth, diff, iters, trace) if return_trace else (hubs, auth, diff, iters)
