@@ -1,4 +1,6 @@
-// Louvain modularity clustering (single GPU; the multi-GPU driver is at the end).
+// Louvain modularity clustering.  One level loop (run_levels) serves one GPU and
+// several: it reaches the clusters through a store, sg_clusters (dense arrays) or
+// mg_clusters (owner-sharded; the multi-GPU section at the end).
 //
 // Reference: cpp/src/community/louvain_impl.cuh:46-301 (level loop, dendrogram,
 // flatten), community/detail/common_methods.cuh:49-382 (delta-modularity local
@@ -181,22 +183,23 @@ __global__ void k_move(uint32_t const* uu, gain_t const* best, int64_t n, uint32
   }
 }
 
-struct sumsq_f {
-  double const* a;
-  uint8_t const* p;
-  __device__ double operator()(size_t i) const { return p[i] ? a[i] * a[i] : 0.0; }
-};
 struct plain_f {
   double const* w;
   __device__ double operator()(size_t i) const { return w[i]; }
 };
-
-// self-loop weight of edge e (its row is src[e] + base)
-__global__ void k_has_edges(int64_t const* off, int64_t n, uint8_t* has)
-{
-  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x)
-    has[v] = off[v + 1] > off[v] ? 1 : 0;
-}
+// a_c^2 of the present clusters, read off their fixed-point weights (the a and present
+// that k_cluster_vals hands the sweep)
+struct sumsq_fixed_f {
+  long long const* afix;
+  int const* pcnt;
+  double inv;
+  int all_present;
+  __device__ double operator()(int64_t i) const
+  {
+    double const a = (double)afix[i] * inv;
+    return (all_present || pcnt[i] > 0) ? a * a : 0.0;
+  }
+};
 
 // contraction
 // compact pair key label(u) << cb | label(v) (cb = label bits; see k_sweep_keys)
@@ -248,10 +251,11 @@ __global__ void k_compact_labels(uint32_t const* used, uint32_t const* pos, uint
     }
 }
 
-__global__ void k_new_ids(uint32_t const* nmap, int64_t n, uint32_t* new_of_label)
+// new ids first, first + 1, ... in nmap's order (first: the owner's range on several GPUs)
+__global__ void k_new_ids(uint32_t const* nmap, int64_t n, uint32_t first, uint32_t* new_of_label)
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    new_of_label[nmap[i]] = (uint32_t)i;
+    new_of_label[nmap[i]] = first + (uint32_t)i;
 }
 
 // (l(u) << 32 | l(v)) -> compact (new(l(u)) << cb | new(l(v)))
@@ -1112,13 +1116,15 @@ __global__ void k_big_info(int64_t const* rows, int64_t const* off, int64_t n, i
   }
 }
 
-// Heavy-row schedule on the device (plan_big_rows' host loop and its uploads were a
-// 2.2 ms gap per level at RMAT-23).  Per heavy row j (rows[j], ascending): segments of
-// kBigSeg edges, 2^logb buckets, partial slots = degree, bucket-offset slots.  Pass 0
-// counts (cnt[4][n + 1], a zero after each list so the exclusive scans end with the
-// totals) and flags rows the LDS passes cannot take (the host plan then runs as
-// before); pass 1 writes big_row / big_seg / the (row, bucket) blocks at the scanned
-// positions.  Segment order, buckets and offsets are plan_big_rows' exactly.
+// Heavy-row schedule, built on the device (a host loop and its uploads were a 2.2 ms
+// gap per level at RMAT-23).  Per heavy row j (rows[j], ascending): segments of
+// kBigSeg edges, 2^logb buckets, partial slots = degree, bucket-offset slots.  A row
+// the LDS passes cannot take (too many segments, or a bucket could outgrow its table)
+// is not taken: it counts nothing and goes to the sort path.  Pass 0 counts
+// (cnt[5][n + 1]: segments, bucket blocks, bucket-offset slots, partial slots, taken;
+// a zero after each list so the exclusive scans end with the totals); pass 1 writes
+// big_row / big_seg / the (row, bucket) blocks of taken row j at the scanned positions,
+// indexed by the row's rank i among the taken rows, and lists the others in `rest`.
 __device__ __forceinline__ int ceil_log2_dev(int64_t x)
 {
   int l = 0;
@@ -1127,23 +1133,29 @@ __device__ __forceinline__ int ceil_log2_dev(int64_t x)
 }
 
 __global__ void k_big_plan(int64_t const* rows, int64_t const* off, int64_t n, int64_t maxdeg, int pass,
-                           u64* cnt, u64 const* pos, big_row* brows, big_seg* bsegs, big_bblk* bblk, int* rest)
+                           u64* cnt, u64 const* pos, big_row* brows, big_seg* bsegs, big_bblk* bblk, int64_t* rest)
 {
   for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
     int64_t const r = rows[j], first = off[r], d = off[r + 1] - first;
     int64_t const nseg = (d + kBigSeg - 1) / kBigSeg;
+    bool const taken   = !(nseg > kBigMaxSegs || d > maxdeg);
     bool const single  = nseg == 1;
-    int const logb     = single ? 0 : min(ceil_log2_dev((d + kBigPerBucket - 1) / kBigPerBucket),
-                                          ceil_log2_dev(kBigMaxBuckets));
-    int64_t const nbk  = single ? 0 : (int64_t(1) << logb);
+    int const logb     = single || !taken ? 0 : min(ceil_log2_dev((d + kBigPerBucket - 1) / kBigPerBucket),
+                                                    ceil_log2_dev(kBigMaxBuckets));
+    int64_t const nbk  = single || !taken ? 0 : (int64_t(1) << logb);
     if (pass == 0) {
-      if (nseg > kBigMaxSegs || d > maxdeg) atomicOr(rest, 1);
-      cnt[0 * (n + 1) + j] = (u64)nseg;
+      cnt[0 * (n + 1) + j] = taken ? (u64)nseg : 0ull;
       cnt[1 * (n + 1) + j] = (u64)nbk;
-      cnt[2 * (n + 1) + j] = single ? 0ull : (u64)(nseg * (nbk + 1));
-      cnt[3 * (n + 1) + j] = (u64)d;
+      cnt[2 * (n + 1) + j] = single || !taken ? 0ull : (u64)(nseg * (nbk + 1));
+      cnt[3 * (n + 1) + j] = taken ? (u64)d : 0ull;
+      cnt[4 * (n + 1) + j] = taken ? 1ull : 0ull;
       if (j == 0)
-        for (int q = 0; q < 4; ++q) cnt[q * (n + 1) + n] = 0ull;
+        for (int q = 0; q < 5; ++q) cnt[q * (n + 1) + n] = 0ull;
+      continue;
+    }
+    int64_t const i = (int64_t)pos[4 * (n + 1) + j];  // taken rows before row j
+    if (!taken) {
+      rest[j - i] = r;
       continue;
     }
     int64_t const sb = (int64_t)pos[0 * (n + 1) + j], bb = (int64_t)pos[1 * (n + 1) + j];
@@ -1156,14 +1168,14 @@ __global__ void k_big_plan(int64_t const* rows, int64_t const* off, int64_t n, i
     rw.send   = (uint32_t)(sb + nseg);
     rw.bbeg   = (uint32_t)bb;
     rw.single = single ? 1u : 0u;
-    brows[j]  = rw;
+    brows[i]  = rw;
     for (int64_t q = 0; q < nseg; ++q) {
       big_seg sg;
       sg.e0    = first + q * kBigSeg;
       sg.e1    = min(first + d, sg.e0 + kBigSeg);
       sg.pbase = pb + q * kBigSeg;
       sg.boff  = single ? ob : ob + q * (nbk + 1);
-      sg.j     = (uint32_t)j;
+      sg.j     = (uint32_t)i;
       sg.pad   = 0;
       bsegs[sb + q] = sg;
     }
@@ -1171,7 +1183,7 @@ __global__ void k_big_plan(int64_t const* rows, int64_t const* off, int64_t n, i
       big_bblk k;
       k.ob         = ob;
       k.pb         = pb;
-      k.j          = (uint32_t)j;
+      k.j          = (uint32_t)i;
       k.u          = (uint32_t)r;
       k.b          = (uint32_t)b;
       k.ns         = (uint32_t)nseg;
@@ -1182,10 +1194,9 @@ __global__ void k_big_plan(int64_t const* rows, int64_t const* off, int64_t n, i
   }
 }
 
-__global__ void k_plan_totals(u64 const* pos, int64_t n, int const* rest, u64* tot)
+__global__ void k_plan_totals(u64 const* pos, int64_t n, u64* tot)
 {
-  if (threadIdx.x < 4) tot[threadIdx.x] = pos[threadIdx.x * (n + 1) + n];
-  if (threadIdx.x == 4) tot[4] = (u64)*rest;
+  if (threadIdx.x < 5) tot[threadIdx.x] = pos[threadIdx.x * (n + 1) + n];
 }
 
 // the two chunk-walk totals (chunks, heavy rows) in one read
@@ -1199,15 +1210,27 @@ __global__ void k_walk_totals(int64_t const* cp, uint32_t const* cc, int64_t con
 // ---------------------------------------------------------------- driver
 struct louvain_state {
   hipStream_t s;
-  double m;
+  double m;  // total edge weight (constant over the levels; set_total_weight)
+  // Cluster weights are 64-bit fixed-point totals at scale 2^(60 - e), m < 2^e: every
+  // move adds its vertex's K to the new cluster and takes it from the old one, integer
+  // adds that give the same totals in any order and on any number of GPUs
+  double ascale = 0, ainv = 0;
   double gamma;
   comm_t* comm = nullptr;  // multi-GPU: the world communicator; nullptr on one GPU
   dbuf<double> scratch;    // device_sum partials
   dbuf<double> scal;       // 2 scalars
   size_t bytes = 0;        // multi-GPU: bytes this rank sent in the exchanges being counted
+  size_t sweeps = 0, sweep_bytes = 0;  // sweeps run, and the bytes of all of them
   tuning_t tune;           // the handle's A/B switches (louvain_*)
   bool trace = false;      // CGX_LOUVAIN_TRACE: per-level plan statistics on stderr (measurement only)
   louvain_state(hipStream_t st, tuning_t const& t) : s(st), scratch(1024, st), scal(2, st), tune(t) {}
+  void set_total_weight(double total)
+  {
+    m           = total;
+    int const e = m > 0 ? std::ilogb(m) + 1 : 0;
+    ascale      = std::ldexp(1.0, 60 - e);
+    ainv        = std::ldexp(1.0, e - 60);
+  }
 };
 
 // k[v] = weight of row v, self[v] = its self-loop weight, has_edges[v], in one pass
@@ -1401,10 +1424,14 @@ void vertex_weights(louvain_state& S, level_graph const& g, int64_t const* off, 
 // (self loops included), so sum_rows own = sum of w over edges inside clusters.  The
 // level loop runs the next sweep before deciding (one extra, discarded sweep per
 // level) instead of an edge pass per sweep (1.7 ms at RMAT-23 level 0).
-double modularity_own(louvain_state& S, level_graph const& g, double const* own, double const* a, uint8_t const* present)
+// afix / pcnt: the fixed-point weights and member counts of the nr cluster ids this rank
+// owns (its rows' ids), read as the sweep's view read them (all_present).
+double modularity(louvain_state& S, int64_t nr, double const* own, long long const* afix, int const* pcnt,
+                  bool all_present)
 {
-  device_sum(plain_f{own}, (size_t)g.nrows, S.scal.data(), S.scratch.data(), S.s);
-  device_sum(sumsq_f{a + g.base, present + g.base}, (size_t)g.nrows, S.scal.data() + 1, S.scratch.data(), S.s);
+  device_sum(plain_f{own}, (size_t)nr, S.scal.data(), S.scratch.data(), S.s);
+  device_sum(sumsq_fixed_f{afix, pcnt, S.ainv, all_present ? 1 : 0}, (size_t)nr, S.scal.data() + 1, S.scratch.data(),
+             S.s);
   if (S.comm) S.comm->allreduce<double>(S.scal.data(), S.scal.data(), 2, CGX_COMM_SUM, S.s);
   auto hv = to_host(S.scal.data(), 2, S.s);
   return hv[0] / S.m - (S.gamma * hv[1]) / (S.m * S.m);
@@ -1417,12 +1444,12 @@ void sweep_sorted(louvain_state& S, level_graph const& g, uint32_t const* src, u
                   uint8_t const* present, bool up_down, double* own)
 {
   hipStream_t s = S.s;
-  int64_t nv = g.nv, nr = g.nrows;
+  int64_t const nr    = g.nrows;
   uint32_t const base = (uint32_t)g.base;
   if (ne == 0) return;
   dbuf<u64> keys(ne, s), keys2(ne, s);
   dbuf<double> w2(ne, s), psum(ne, s);
-  int const cb = bits_for((unsigned long long)std::max<int64_t>(nv - 1, 0));
+  int const cb = bits_for((unsigned long long)std::max<int64_t>(g.nv - 1, 0));
   hipLaunchKernelGGL(k_sweep_keys, dim3(blocks(ne)), dim3(kBlock), 0, s, src, dst, c, ne, cb, keys.data());
   CGX_LAUNCH_CHECK();
   radix_sort_pairs<u64, double>(keys.data(), keys2.data(), w, w2.data(), (size_t)ne, 0,
@@ -1447,7 +1474,6 @@ void sweep_sorted(louvain_state& S, level_graph const& g, uint32_t const* src, u
                              rocprim::equal_to<uint32_t>(), s);
   hipLaunchKernelGGL(k_move, dim3(blocks(nu)), dim3(kBlock), 0, s, uu.data(), best.data(), nu, c, base, next, up_down);
   CGX_LAUNCH_CHECK();
-  (void)nv;
 }
 
 // Per-level schedule of the local move (the level graph is fixed across its
@@ -1477,14 +1503,14 @@ struct sweep_plan {
   dbuf<u64> pval;
   dbuf<int32_t> boffs;
   dbuf<int> overflow;
-  std::vector<int64_t> big, big_first, big_deg;  // every heavy row (host; filled when a host plan needs them)
+  std::vector<int64_t> big, big_first, big_deg;  // every heavy row (host; filled when the sort path needs them)
   dbuf<int64_t> bigd;                            // the heavy rows, ascending (device)
   dbuf<double> ag;                               // the sweep's gain weights (k_gain_weights)
   int64_t tb = 0;
 };
 
-// the heavy rows' (row, first edge, degree) on the host, for the host plan and the
-// sort-path fallback
+// the heavy rows' (row, first edge, degree) on the host, for the sort path (rows not
+// taken, the overflow fallback)
 inline void big_rows_to_host(hipStream_t s, sweep_plan& P)
 {
   if (P.tb == 0 || !P.big.empty()) return;
@@ -1504,126 +1530,55 @@ inline int big_bucket_cap(tuning_t const& tu)
   return v > 0 && v < kBktCap ? v : kBktCap;
 }
 
-inline int ceil_log2(int64_t x)
-{
-  int l = 0;
-  while ((1ll << l) < x) ++l;
-  return l;
-}
-
-// the heavy rows the LDS passes take; returns the others (sort path)
+// the heavy rows the LDS passes take (k_big_plan); returns the others (sort path)
 std::vector<int64_t> plan_big_rows(hipStream_t s, sweep_plan& P, tuning_t const& tu)
 {
-  std::vector<int64_t> const& big = P.big;
-  std::vector<int64_t> rest;
-  std::vector<big_row> rows;
-  std::vector<big_seg> segs;
-  std::vector<big_bblk> bb;
-  int64_t pstart = 0, boff = 0;
+  int64_t const n = P.tb;
+  if (n == 0) return {};
   int64_t const md     = tu.louvain_big_maxdeg;  // tests: a lower limit
   int64_t const maxdeg = std::min<int64_t>(md > 0 ? md : INT64_MAX, (int64_t)kBigMaxBuckets * kBktCap * 4 / 5);
-  for (size_t q = 0; q < big.size(); ++q) {
-    int64_t const r = big[q], first = P.big_first[q], d = P.big_deg[q];
-    int64_t const nseg  = (d + kBigSeg - 1) / kBigSeg;
-    if (nseg > kBigMaxSegs || d > maxdeg) {
-      rest.push_back(r);  // a bucket could outgrow its table
-      continue;
-    }
-    int64_t const j = (int64_t)rows.size();
-    rows.emplace_back();
-    bool const single = nseg == 1;
-    int const logb    = single ? 0 : std::min(ceil_log2((d + kBigPerBucket - 1) / kBigPerBucket), ceil_log2(kBigMaxBuckets));
-    big_row& rw = rows[j];
-    rw.first    = first;
-    rw.row      = (uint32_t)r;
-    rw.logb     = (uint32_t)logb;
-    rw.sbeg     = (uint32_t)segs.size();
-    rw.bbeg     = (uint32_t)bb.size();
-    for (int64_t q = 0; q < nseg; ++q) {
-      big_seg sg;
-      sg.e0    = first + q * kBigSeg;
-      sg.e1    = std::min(first + d, sg.e0 + kBigSeg);
-      sg.pbase = pstart + q * kBigSeg;
-      sg.boff  = boff;
-      sg.j     = (uint32_t)j;
-      sg.pad   = 0;
-      if (!single) boff += (1 << logb) + 1;
-      segs.push_back(sg);
-    }
-    rw.send   = (uint32_t)segs.size();
-    rw.single = single ? 1u : 0u;
-    if (!single)
-      for (int b = 0; b < (1 << logb); ++b)
-        bb.push_back(big_bblk{segs[rw.sbeg].boff, segs[rw.sbeg].pbase, (uint32_t)j, (uint32_t)r, (uint32_t)b,
-                              (uint32_t)nseg, (uint32_t)logb, 0u});
-    pstart += d;
-  }
-  int64_t const nb = (int64_t)rows.size();
-  if (nb == 0) return rest;
-  P.nbig     = nb;
-  P.nsegs    = (int64_t)segs.size();
-  P.nbblocks = (int64_t)bb.size();
-  P.brows.resize(nb, s);
-  P.bsegs.resize(P.nsegs, s);
-  P.bblocks.resize(P.nbblocks, s);
-  to_device(P.brows.data(), rows.data(), nb, s);
-  to_device(P.bsegs.data(), segs.data(), P.nsegs, s);
-  to_device(P.bblocks.data(), bb.data(), P.nbblocks, s);
-  P.own.resize(nb, s);
-  P.best_q.resize(P.nbblocks, s);
-  P.best_c.resize(P.nbblocks, s);
-  P.pkey.resize(pstart, s);
-  P.pval.resize(pstart, s);
-  P.boffs.resize(boff, s);
-  P.overflow.resize(1, s);
-  HIP_CHECK(hipStreamSynchronize(s));  // host vectors go out of scope
-  P.big_hash = true;
-  return rest;
-}
-
-// plan_big_rows on the device (k_big_plan); false: some heavy row needs the sort path,
-// and nothing was planned (the caller runs the host plan)
-bool plan_big_rows_device(hipStream_t s, sweep_plan& P, tuning_t const& tu)
-{
-  int64_t const n = P.tb;
-  if (n == 0) return true;
-  int64_t const md     = tu.louvain_big_maxdeg;
-  int64_t const maxdeg = std::min<int64_t>(md > 0 ? md : INT64_MAX, (int64_t)kBigMaxBuckets * kBktCap * 4 / 5);
-  dbuf<u64> cnt(4 * (n + 1), s), pos(4 * (n + 1), s);
-  dbuf<int> rest(1, s);
-  fill<int>(rest.data(), 1, 0, s);
+  dbuf<u64> cnt(5 * (n + 1), s), pos(5 * (n + 1), s);
   unsigned const g = grid_for(n, kBlock, 16384);
   hipLaunchKernelGGL(k_big_plan, dim3(g), dim3(kBlock), 0, s, P.bigd.data(), P.off, n, maxdeg, 0, cnt.data(),
-                     (u64 const*)nullptr, (big_row*)nullptr, (big_seg*)nullptr, (big_bblk*)nullptr, rest.data());
+                     (u64 const*)nullptr, (big_row*)nullptr, (big_seg*)nullptr, (big_bblk*)nullptr,
+                     (int64_t*)nullptr);
   CGX_LAUNCH_CHECK();
-  for (int q = 0; q < 4; ++q)
+  for (int q = 0; q < 5; ++q)
     exclusive_scan<u64, u64>(cnt.data() + q * (n + 1), pos.data() + q * (n + 1), (size_t)(n + 1), s);
-  // one read: the four totals and the rest flag
+  // one read: the four totals and the taken count
   dbuf<u64> tot(5, s);
-  hipLaunchKernelGGL(k_plan_totals, dim3(1), dim3(64), 0, s, pos.data(), n, rest.data(), tot.data());
+  hipLaunchKernelGGL(k_plan_totals, dim3(1), dim3(64), 0, s, pos.data(), n, tot.data());
   CGX_LAUNCH_CHECK();
-  auto const t = to_host(tot.data(), 5, s);
-  if (t[4]) return false;
-  P.nbig     = n;
+  auto const t     = to_host(tot.data(), 5, s);
+  int64_t const nt = (int64_t)t[4];
+  if (nt == 0) {  // every heavy row on the sort path
+    big_rows_to_host(s, P);
+    return P.big;
+  }
+  P.nbig     = nt;
   P.nsegs    = (int64_t)t[0];
   P.nbblocks = (int64_t)t[1];
-  P.brows.resize(n, s);
+  P.brows.resize(nt, s);
   P.bsegs.resize(P.nsegs, s);
   P.bblocks.resize(std::max<int64_t>(P.nbblocks, 1), s);
+  dbuf<int64_t> rest;
+  if (nt < n) rest.resize(n - nt, s);
   hipLaunchKernelGGL(k_big_plan, dim3(g), dim3(kBlock), 0, s, P.bigd.data(), P.off, n, maxdeg, 1, (u64*)nullptr,
                      pos.data(), P.brows.data(), P.bsegs.data(), P.bblocks.data(), rest.data());
   CGX_LAUNCH_CHECK();
-  P.own.resize(n, s);
+  P.own.resize(nt, s);
   P.best_q.resize(std::max<int64_t>(P.nbblocks, 1), s);
   P.best_c.resize(std::max<int64_t>(P.nbblocks, 1), s);
   P.pkey.resize(std::max<u64>(t[3], 1), s);
   P.pval.resize(std::max<u64>(t[3], 1), s);
   P.boffs.resize(std::max<u64>(t[2], 1), s);
   P.overflow.resize(1, s);
-  HIP_CHECK(hipStreamSynchronize(s));  // cnt / pos / rest / tot go out of scope
+  auto out = to_host(rest.data(), rest.n, s);
+  HIP_CHECK(hipStreamSynchronize(s));  // cnt / pos / tot / rest go out of scope
   P.big_hash = true;
-  return true;
+  return out;
 }
+
 
 // the edges of `rows` for the sort path: the level COO itself when they are a
 // prefix of the rows, else gathered
@@ -1701,9 +1656,11 @@ void plan_sweeps(louvain_state& S, level_graph const& g, int64_t const* off, u64
   CGX_LAUNCH_CHECK();
   P.off = off;
   // (louvain_big_hash = 0: heavy rows on the sort path, A/B)
-  if (!S.tune.louvain_big_hash || !plan_big_rows_device(s, P, S.tune)) {
+  if (!S.tune.louvain_big_hash) big_rows_to_host(s, P);
+  auto const rest = S.tune.louvain_big_hash ? plan_big_rows(s, P, S.tune) : P.big;
+  if (!rest.empty()) {
     big_rows_to_host(s, P);
-    build_sort_coo(s, g, P, S.tune.louvain_big_hash ? plan_big_rows(s, P, S.tune) : P.big);
+    build_sort_coo(s, g, P, rest);
   }
   HIP_CHECK(hipStreamSynchronize(s));  // the walk's scratch goes out of scope
   P.hash = true;
@@ -1893,7 +1850,7 @@ level_graph contract(louvain_state& S, level_graph const& g, uint32_t* labels)
   iota<uint32_t>(uniq.data(), nu, 0u, s);
   radix_sort_pairs<uint32_t, uint32_t>(deg.data(), udeg2.data(), uniq.data(), nmap.data(), (size_t)nu, 0,
                                        bits_for((unsigned long long)std::max<int64_t>(nce, 1)), s, /*descending=*/true);
-  hipLaunchKernelGGL(k_new_ids, dim3(blocks(nu)), dim3(kBlock), 0, s, nmap.data(), nu, nl.data());
+  hipLaunchKernelGGL(k_new_ids, dim3(blocks(nu)), dim3(kBlock), 0, s, nmap.data(), nu, 0u, nl.data());
   CGX_LAUNCH_CHECK();
   level_graph out;
   out.nv    = nu;
@@ -1913,6 +1870,189 @@ level_graph contract(louvain_state& S, level_graph const& g, uint32_t* labels)
   hipLaunchKernelGGL(k_gather_u32, dim3(blocks(nv)), dim3(kBlock), 0, s, nl.data(), labels, nv);
   CGX_LAUNCH_CHECK();
   return out;
+}
+
+// what a sweep reads of the clustering: c[local id] = cluster, and the weight and
+// present flag of each of the na cluster ids that c names
+struct cluster_view {
+  uint32_t const* c;
+  double const* a;
+  uint8_t const* present;
+  int64_t na;
+};
+
+// The cluster store of one GPU: every id of the level is a row here, so the clusters
+// and their fixed-point weights are dense arrays over the level's ids.  (mg_clusters
+// below is the store of several GPUs; run_levels drives either.)
+struct sg_clusters {
+  int64_t nv = 0;
+  dbuf<long long> kfix, afix_;
+  dbuf<int> pcnt_;
+  dbuf<uint32_t> clusters;
+  dbuf<double> a;
+  dbuf<uint8_t> present;
+  long long const* afix() const { return afix_.data(); }
+  int const* pcnt() const { return pcnt_.data(); }
+
+  // singleton clusters: cluster v holds vertex v's weight
+  void begin_level(louvain_state& S, level_graph& g, double const* k, uint8_t const* has_edges)
+  {
+    hipStream_t s = S.s;
+    nv            = g.nv;
+    a.resize(nv, s);
+    present.resize(nv, s);
+    kfix.resize(nv, s);
+    afix_.resize(nv, s);
+    pcnt_.resize(nv, s);
+    hipLaunchKernelGGL(k_to_fixed, dim3(blocks(nv)), dim3(kBlock), 0, s, k, nv, S.ascale, kfix.data());
+    CGX_LAUNCH_CHECK();
+    HIP_CHECK(hipMemcpyAsync(afix_.data(), kfix.data(), nv * sizeof(long long), hipMemcpyDeviceToDevice, s));
+    convert<int, uint8_t>(pcnt_.data(), has_edges, nv, s);
+    clusters.resize(nv, s);
+    iota<uint32_t>(clusters.data(), nv, 0u, s);
+  }
+  cluster_view view(louvain_state& S, bool all_present)
+  {
+    hipLaunchKernelGGL(k_cluster_vals, dim3(blocks(nv)), dim3(kBlock), 0, S.s, afix_.data(), pcnt_.data(), nv, S.ainv,
+                       all_present ? 1 : 0, a.data(), present.data());
+    CGX_LAUNCH_CHECK();
+    return {clusters.data(), a.data(), present.data(), nv};
+  }
+  // clusters <- the sweep's result (next[row]); one pass over the vertices moves their
+  // weights (where re-summing sorted every vertex by cluster: ~0.3 ms a sweep at RMAT-23)
+  void advance(louvain_state& S, dbuf<uint32_t>& next, uint8_t const* has_edges)
+  {
+    hipLaunchKernelGGL(k_apply_moves, dim3(blocks(nv)), dim3(kBlock), 0, S.s, clusters.data(), next.data(), nv,
+                       kfix.data(), has_edges, afix_.data(), pcnt_.data());
+    CGX_LAUNCH_CHECK();
+    std::swap(clusters, next);
+  }
+  void keep(louvain_state& S, uint32_t* level)
+  {
+    HIP_CHECK(hipMemcpyAsync(level, clusters.data(), nv * sizeof(uint32_t), hipMemcpyDeviceToDevice, S.s));
+  }
+  void release()
+  {
+    a.free();
+    kfix.free();
+    afix_.free();
+    pcnt_.free();
+    clusters.free();
+    present.free();
+  }
+  void end_level() { release(); }
+  level_graph contract_level(louvain_state& S, level_graph const& g, uint32_t* level) { return contract(S, g, level); }
+};
+
+// The level loop of both modes (louvain_impl.cuh:46-237): per level the row offsets,
+// the vertex weights, singleton clusters in the store C and the sweep schedule; then
+// sweeps while Q gains more than 1e-4, the up/down restriction alternating, the level's
+// clustering kept whenever Q improved; the loop ends when a level brings no gain, else
+// the level is contracted.  Every sweep returns the internal weight of the clustering it
+// started from (modularity), so sweep k + 1 runs before the loop decides on clustering
+// k.  On several GPUs Q is allreduced, so every rank takes the same branches.  Appends
+// the levels' clusterings (of this rank's rows) to `dendrogram`; returns the best Q.
+template <typename Clusters>
+double run_levels(louvain_state& S, level_graph& cur, size_t max_level, Clusters& C,
+                  std::vector<dbuf<uint32_t>>& dendrogram)
+{
+  hipStream_t s = S.s;
+  // CGX_LOUVAIN_TRACE (measurement only): one GPU prints a line per step with its time;
+  // several print rank 0's bytes per sweep, and with CGX_LOUVAIN_TRACE=2 (debugging)
+  // every rank syncs and names each phase as it ends, so a rank that stops shows where
+  char const* const tv = std::getenv("CGX_LOUVAIN_TRACE");
+  S.trace              = tv != nullptr;
+  bool const sg_trace = S.trace && !S.comm, mg_trace = S.trace && S.comm && S.comm->rank == 0;
+  bool const phases   = S.trace && S.comm && std::atoi(tv) >= 2;
+  auto t_last         = std::chrono::steady_clock::now();
+  auto lap            = [&](char const* what, int64_t nv, int64_t ne, double q) {
+    if (!sg_trace) return;
+    auto t = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[louvain] %-9s nv=%lld ne=%lld q=%.6f %.2f ms\n", what, (long long)nv, (long long)ne, q,
+                 std::chrono::duration<double, std::milli>(t - t_last).count());
+    t_last = t;
+  };
+  auto phase = [&](char const* what, size_t i) {
+    if (!phases) return;
+    HIP_CHECK(hipStreamSynchronize(s));
+    std::fprintf(stderr, "[louvain-mg r%d] %s %zu\n", S.comm->rank, what, i);
+  };
+  double best_q = -1.0;
+  lap("start", cur.nv, cur.ne, 0.0);
+  while (dendrogram.size() < max_level) {
+    size_t const li  = dendrogram.size();
+    int64_t const nv = cur.nv, nr = cur.nrows, r1 = std::max<int64_t>(nr, 1);
+    dendrogram.emplace_back(r1, s);
+    uint32_t* level = dendrogram.back().data();
+    iota<uint32_t>(level, nr, (uint32_t)cur.base, s);
+    // vertex weights, cluster keys = every vertex (louvain_impl.cuh:91-103); on several
+    // GPUs the weights are taken on the global destinations (self loops: dst == row +
+    // base) before begin_level turns the destinations into local ids
+    dbuf<int64_t> off(nr + 1, s);
+    lower_bounds(key_of<uint32_t>{cur.src.data()}, cur.ne, target_index{}, nr, off.data(), s);  // first edge of row v
+    dbuf<double> k(r1, s), self(r1, s);
+    dbuf<uint8_t> has_edges(r1, s);
+    dbuf<u64> vstats(2, s);
+    vertex_weights(S, cur, off.data(), k.data(), self.data(), has_edges.data(), vstats.data());
+    S.bytes = 0;
+    C.begin_level(S, cur, k.data(), has_edges.data());
+    phase("setup", li);
+    size_t const setup_bytes = S.bytes;
+    dbuf<uint32_t> next(r1, s);
+    sweep_plan plan;
+    plan_sweeps(S, cur, off.data(), vstats.data(), plan);
+    phase("plan", li + 1);
+    dbuf<double> own(r1, s);
+    bool all_present = true;  // the first sweep sees every vertex present
+    bool up_down     = true;
+    int64_t na       = 0;
+    auto sweep_q     = [&]() {  // view -> sweep -> Q of the clustering the sweep started from
+      cluster_view const v = C.view(S, all_present);
+      na                   = v.na;
+      phase("view", S.sweeps);
+      sweep(S, cur, plan, v.c, next.data(), k.data(), self.data(), v.a, v.present, v.na, up_down, own.data());
+      phase("sweep", S.sweeps);
+      double const q = modularity(S, nr, own.data(), C.afix(), C.pcnt(), all_present);
+      ++S.sweeps;
+      S.sweep_bytes += S.bytes;
+      return q;
+    };
+    S.bytes      = 0;
+    double new_q = sweep_q();
+    if (mg_trace)
+      std::fprintf(stderr, "[louvain-mg] level %zu nv=%lld setup %zu B/rank, sweep %zu B/rank q=%.6f\n", li,
+                   (long long)nv, setup_bytes, S.bytes, new_q);
+    lap("setup", nv, cur.ne, new_q);
+    double cur_q = new_q - 1.0;
+    while (new_q > cur_q + 0.0001) {
+      cur_q   = new_q;
+      S.bytes = 0;
+      C.advance(S, next, has_edges.data());
+      phase("advance", S.sweeps);
+      all_present = false;
+      up_down     = !up_down;
+      new_q       = sweep_q();
+      if (mg_trace)
+        std::fprintf(stderr, "[louvain-mg]   sweep %zu B/rank (%lld referenced clusters) q=%.6f\n", S.bytes,
+                     (long long)na, new_q);
+      if (new_q > cur_q) C.keep(S, level);
+      lap("sweep", nv, cur.ne, new_q);
+    }
+    if (cur_q <= best_q) break;
+    best_q = cur_q;
+    // the level's sweep state goes before the contraction's sort buffers are allocated
+    plan = sweep_plan{};
+    for (auto* b : {&own, &k, &self}) b->free();
+    C.end_level();
+    next.free();
+    has_edges.free();
+    off.free();
+    cur = C.contract_level(S, cur, level);
+    phase("contract", li + 1);
+    lap("contract", cur.nv, cur.ne, best_q);
+  }
+  C.release();
+  return best_q;
 }
 
 template <typename V, typename E, typename R>
@@ -1958,95 +2098,11 @@ void louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, 
   // is the adjacency's; the fp64 values are the same numbers)
   if constexpr (std::is_same_v<R, float>) cur.wf = cur.ne ? adj.weights.data<float>() : nullptr;
   device_sum(plain_f{cur.w.data()}, (size_t)cur.ne, S.scal.data(), S.scratch.data(), s);
-  S.m = to_host_scalar(S.scal.data(), s);  // total edge weight (constant over levels)
+  S.set_total_weight(to_host_scalar(S.scal.data(), s));
 
   std::vector<dbuf<uint32_t>> dendrogram;
-  double best_q = -1.0;
-  bool const trace = std::getenv("CGX_LOUVAIN_TRACE") != nullptr;  // measurement only
-  S.trace          = trace;
-  auto t_last      = std::chrono::steady_clock::now();
-  auto lap         = [&](char const* what, int64_t nv, int64_t ne, double q) {
-    if (!trace) return;
-    auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[louvain] %-9s nv=%lld ne=%lld q=%.6f %.2f ms\n", what, (long long)nv, (long long)ne, q,
-                 std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
-  lap("start", cur.nv, cur.ne, 0.0);
-  while (dendrogram.size() < max_level) {
-    int64_t nv = cur.nv;
-    dendrogram.emplace_back(std::max<int64_t>(nv, 1), s);
-    uint32_t* level = dendrogram.back().data();
-    iota<uint32_t>(level, nv, 0u, s);
-    // vertex weights, cluster keys = every vertex (louvain_impl.cuh:91-103)
-    dbuf<int64_t> off(nv + 1, s);
-    lower_bounds(key_of<uint32_t>{cur.src.data()}, cur.ne, target_index{}, nv, off.data(), s);  // first edge of row v
-    dbuf<double> k(nv, s), self(nv, s), a(nv, s);
-    dbuf<uint8_t> has_edges(nv, s), present(nv, s);
-    dbuf<u64> vstats(2, s);
-    vertex_weights(S, cur, off.data(), k.data(), self.data(), has_edges.data(), vstats.data());
-    // Cluster weights in 64-bit fixed point, as the multi-GPU owners keep them (scale
-    // 2^(60 - e), the total weight < 2^e): every move adds its vertex's K to the new
-    // cluster and takes it from the old one (k_apply_moves), integer adds that give
-    // the same totals in any order -- one pass over the vertices per sweep where the
-    // re-summation sorted every vertex by cluster (~0.3 ms a sweep at RMAT-23).  a and
-    // present are read off them; the first sweep sees every vertex present.
-    int const ea        = S.m > 0 ? std::ilogb(S.m) + 1 : 0;
-    double const ascale = std::ldexp(1.0, 60 - ea), ainv = std::ldexp(1.0, ea - 60);
-    dbuf<long long> kfix(nv, s), afix(nv, s);
-    dbuf<int> pcnt(nv, s);
-    hipLaunchKernelGGL(k_to_fixed, dim3(blocks(nv)), dim3(kBlock), 0, s, k.data(), nv, ascale, kfix.data());
-    CGX_LAUNCH_CHECK();
-    HIP_CHECK(hipMemcpyAsync(afix.data(), kfix.data(), nv * sizeof(long long), hipMemcpyDeviceToDevice, s));
-    convert<int, uint8_t>(pcnt.data(), has_edges.data(), nv, s);
-    hipLaunchKernelGGL(k_cluster_vals, dim3(blocks(nv)), dim3(kBlock), 0, s, afix.data(), pcnt.data(), nv, ainv, 1,
-                       a.data(), present.data());
-    CGX_LAUNCH_CHECK();
-    dbuf<uint32_t> clusters(nv, s), next(nv, s);
-    iota<uint32_t>(clusters.data(), nv, 0u, s);
-    sweep_plan plan;
-    plan_sweeps(S, cur, off.data(), vstats.data(), plan);
-    dbuf<double> own(nv, s);
-    // every sweep also returns the internal weight of the clustering it started from
-    // (modularity_own): sweep k + 1 runs before the loop decides on clustering k
-    bool up_down = true;
-    sweep(S, cur, plan, clusters.data(), next.data(), k.data(), self.data(), a.data(), present.data(), nv, up_down,
-          own.data());
-    double new_q = modularity_own(S, cur, own.data(), a.data(), present.data());
-    lap("setup", nv, cur.ne, new_q);
-    double cur_q = new_q - 1.0;
-    while (new_q > cur_q + 0.0001) {
-      cur_q = new_q;
-      hipLaunchKernelGGL(k_apply_moves, dim3(blocks(nv)), dim3(kBlock), 0, s, clusters.data(), next.data(), nv,
-                         kfix.data(), has_edges.data(), afix.data(), pcnt.data());
-      CGX_LAUNCH_CHECK();
-      std::swap(clusters, next);
-      hipLaunchKernelGGL(k_cluster_vals, dim3(blocks(nv)), dim3(kBlock), 0, s, afix.data(), pcnt.data(), nv, ainv, 0,
-                         a.data(), present.data());
-      CGX_LAUNCH_CHECK();
-      up_down = !up_down;
-      sweep(S, cur, plan, clusters.data(), next.data(), k.data(), self.data(), a.data(), present.data(), nv, up_down,
-            own.data());
-      new_q = modularity_own(S, cur, own.data(), a.data(), present.data());
-      if (new_q > cur_q)
-        HIP_CHECK(hipMemcpyAsync(level, clusters.data(), nv * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-      lap("sweep", nv, cur.ne, new_q);
-    }
-    if (cur_q <= best_q) break;
-    best_q = cur_q;
-    // the level's sweep state goes before the contraction's sort buffers are allocated
-    plan = sweep_plan{};
-    for (auto* b : {&own, &k, &self, &a}) b->free();
-    kfix.free();
-    afix.free();
-    pcnt.free();
-    for (auto* b : {&clusters, &next}) b->free();
-    has_edges.free();
-    present.free();
-    off.free();
-    cur = contract(S, cur, level);
-    lap("contract", cur.nv, cur.ne, best_q);
-  }
+  sg_clusters C;
+  double const best_q = run_levels(S, cur, max_level, C, dendrogram);
   // flatten_dendrogram (louvain_impl.cuh:239-255)
   dbuf<uint32_t> flat(nv0, s);
   iota<uint32_t>(flat.data(), nv0, 0u, s);
@@ -2096,8 +2152,8 @@ void louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, 
 //    mirrors), reported per sweep (CGX_LOUVAIN_TRACE) and as the handle statistic
 //    last_louvain_sweep_bytes;
 //  * modularity: per-rank partials (own internal weight, own cluster ids' a_c^2)
-//    and a 2-double allreduce, so every rank takes the same branch of the level
-//    loop;
+//    and a 2-double allreduce (modularity above), so every rank takes the same
+//    branch of the level loop;
 //  * contraction: coarse pairs (label(u), label(v)) are reduced locally, sent to
 //    the owner of label(u) and merged there; each owner numbers its used labels by
 //    descending coarse degree (ties: ascending label), the owners' ranges stay
@@ -2106,17 +2162,13 @@ void louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, 
 //  * flatten: each level's owners answer for the ids the owned level-0 vertices
 //    have reached.
 //
-// With one rank this is the single-GPU algorithm (same ids, same exact sums for
-// integer weights).  With several, every decision is the single-GPU decision on the
+// The level loop is run_levels, the single-GPU one: this section is its cluster store
+// (mg_clusters over mg_setup_level / mg_view / mg_advance), level 0, the contraction and
+// the flatten.  With one rank it is therefore the single-GPU algorithm (same ids, same
+// fixed-point sums).  With several, every decision is the single-GPU decision on the
 // same (MG-numbered) level graph whenever the sums are exact (integer weights),
 // which is what the reference's MG test checks level by level
 // (mg_louvain_test.cpp:82-151).
-
-__global__ void k_new_ids_off(uint32_t const* nmap, int64_t n, uint32_t first, uint32_t* new_of_label)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    new_of_label[nmap[i]] = first + (uint32_t)i;
-}
 
 // level 0: the 2D block's edges -> rows of this rank's sources
 template <typename V, typename R>
@@ -2165,7 +2217,7 @@ level_graph mg_level0(handle_t& h, graph_t& g)
 
 // ---------------------------------------------------------------- owner-sharded state
 // Every exchange of the sweep loop goes through these helpers, which also count the
-// bytes this rank sends (S.sweep_bytes; per-sweep figure in DESIGN.md, trace
+// bytes this rank sends (S.bytes; per-sweep figure in DESIGN.md, trace
 // CGX_LOUVAIN_TRACE=1, handle statistic last_louvain_sweep_bytes).
 template <typename T>
 dbuf<T> xchg(louvain_state& S, T const* send, std::vector<size_t> const& counts, std::vector<size_t>& rcounts)
@@ -2231,19 +2283,6 @@ __global__ void k_sub_u32(uint32_t* x, int64_t n, uint32_t lo)
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     x[i] -= lo;
 }
-
-// sum over the owned cluster ids of a_c^2 (present clusters only)
-struct sumsq_fixed_f {
-  long long const* afix;
-  int const* pcnt;
-  double inv;
-  int all_present;
-  __device__ double operator()(int64_t i) const
-  {
-    double const a = (double)afix[i] * inv;
-    return (all_present || pcnt[i] > 0) ? a * a : 0.0;
-  }
-};
 
 // local clusters after the sweep -> global ids; moved rows flagged, the owners'
 // weight deltas listed: (old cluster, -K, -has) and (new cluster, +K, +has) per move
@@ -2349,12 +2388,6 @@ __global__ void k_scatter_table(uint32_t const* tk, uint32_t const* tv, int64_t 
 {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nt; i += (int64_t)gridDim.x * blockDim.x)
     dense[tk[i]] = tv[i];
-}
-
-__global__ void k_lookup_dense(uint32_t* x, int64_t n, uint32_t const* dense)
-{
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    x[i] = dense[x[i]];
 }
 
 // x[i] -> the value of x[i] in the table (keys sorted, every x present)
@@ -2484,7 +2517,6 @@ dbuf<T> collect_by_key(louvain_state& S, uint32_t const* keys, int64_t n, dbuf<i
 // sweep kernels run unchanged on (rows, local ids, local cluster ids).
 struct mg_level {
   int64_t nv = 0, lo = 0, nr = 0, ng = 0;
-  std::vector<int64_t> voff;
   dbuf<int64_t> voff_d;
   dbuf<uint32_t> ghost;     // ng: sorted global ids of remote destinations
   dbuf<uint32_t> mir;       // rows (id - lo) mirrored to other ranks, in requester order
@@ -2493,7 +2525,6 @@ struct mg_level {
   dbuf<uint32_t> c_own, c_gh;  // clusters (global ids) of the rows and of the ghosts
   dbuf<long long> kfix, afix;  // rows' fixed-point weights; owned clusters' fixed-point weights
   dbuf<int> pcnt;              // owned clusters: members with edges
-  double scale = 0, inv = 0;
 };
 
 void mg_setup_level(louvain_state& S, level_graph& g, mg_level& L, uint8_t const* has_edges, double const* k)
@@ -2536,15 +2567,12 @@ void mg_setup_level(louvain_state& S, level_graph& g, mg_level& L, uint8_t const
   L.c_gh.resize(std::max<int64_t>(L.ng, 1), s);
   if (L.ng)
     HIP_CHECK(hipMemcpyAsync(L.c_gh.data(), L.ghost.data(), L.ng * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  // fixed-point cluster weights at the owners: scale 2^(60 - e), sum of all weights < 2^e
-  int const e = S.m > 0 ? std::ilogb(S.m) + 1 : 0;
-  L.scale     = std::ldexp(1.0, 60 - e);
-  L.inv       = std::ldexp(1.0, e - 60);
+  // fixed-point cluster weights at the owners
   L.kfix.resize(r1, s);
   L.afix.resize(r1, s);
   L.pcnt.resize(r1, s);
   if (nr) {
-    hipLaunchKernelGGL(k_to_fixed, dim3(blocks(nr)), dim3(kBlock), 0, s, k, nr, L.scale, L.kfix.data());
+    hipLaunchKernelGGL(k_to_fixed, dim3(blocks(nr)), dim3(kBlock), 0, s, k, nr, S.ascale, L.kfix.data());
     CGX_LAUNCH_CHECK();
     HIP_CHECK(hipMemcpyAsync(L.afix.data(), L.kfix.data(), nr * sizeof(long long), hipMemcpyDeviceToDevice, s));
     convert<int, uint8_t>(L.pcnt.data(), has_edges, nr, s);
@@ -2578,21 +2606,9 @@ void mg_view(louvain_state& S, mg_level& L, bool all_present, mg_sweep_view& W)
   W.a.resize(std::max<int64_t>(W.ncl, 1), s);
   W.present.resize(std::max<int64_t>(W.ncl, 1), s);
   if (W.ncl)
-    hipLaunchKernelGGL(k_cluster_vals, dim3(blocks(W.ncl)), dim3(kBlock), 0, s, af.data(), pc.data(), W.ncl, L.inv,
+    hipLaunchKernelGGL(k_cluster_vals, dim3(blocks(W.ncl)), dim3(kBlock), 0, s, af.data(), pc.data(), W.ncl, S.ainv,
                        all_present ? 1 : 0, W.a.data(), W.present.data());
   CGX_LAUNCH_CHECK();
-}
-
-// Q of the clustering the sweep started from: sum of own(row) (the internal weight
-// by-product of the sweep) and sum of a_c^2 over the owned cluster ids
-double mg_modularity(louvain_state& S, mg_level& L, double const* own, bool all_present)
-{
-  device_sum(plain_f{own}, (size_t)L.nr, S.scal.data(), S.scratch.data(), S.s);
-  device_sum(sumsq_fixed_f{L.afix.data(), L.pcnt.data(), L.inv, all_present ? 1 : 0}, (size_t)L.nr,
-             S.scal.data() + 1, S.scratch.data(), S.s);
-  S.comm->allreduce<double>(S.scal.data(), S.scal.data(), 2, CGX_COMM_SUM, S.s);
-  auto hv = to_host(S.scal.data(), 2, S.s);
-  return hv[0] / S.m - (S.gamma * hv[1]) / (S.m * S.m);
 }
 
 // clusters <- the sweep's result: rows' new global clusters, the owners' weights
@@ -2786,7 +2802,7 @@ level_graph mg_contract(louvain_state& S, level_graph const& g, mg_level& L, uin
   for (int q = 0; q < P; ++q) nvoff[q + 1] = nvoff[q] + all_nu[q];
   uint32_t const new_lo = (uint32_t)nvoff[p];
   if (nu)
-    hipLaunchKernelGGL(k_new_ids_off, dim3(blocks(nu)), dim3(kBlock), 0, s, nmap.data(), nu, new_lo, nl_own.data());
+    hipLaunchKernelGGL(k_new_ids, dim3(blocks(nu)), dim3(kBlock), 0, s, nmap.data(), nu, new_lo, nl_own.data());
   CGX_LAUNCH_CHECK();
   // (nl_own: the new id of every used label, indexed by label - lo)
   // 4. new ids of the labels this rank still needs: label(v) of its merged pairs and
@@ -2823,11 +2839,72 @@ level_graph mg_contract(louvain_state& S, level_graph const& g, mg_level& L, uin
     }
     split_row_keys(mk.data(), nm, out.src.data(), out.dst.data(), s);
   }
-  if (nr) hipLaunchKernelGGL(k_lookup_dense, dim3(blocks(nr)), dim3(kBlock), 0, s, lab_own, nr, dense.data());
+  if (nr) hipLaunchKernelGGL(k_gather_u32, dim3(blocks(nr)), dim3(kBlock), 0, s, dense.data(), lab_own, nr);
   CGX_LAUNCH_CHECK();
   voff = nvoff;
   return out;
 }
+
+// The cluster store of several GPUs (run_levels' Clusters; sg_clusters is the dense
+// one): the level's owner-sharded state L, the current sweep's view W, and what the
+// flatten and the handle statistics need of the levels.
+struct mg_clusters {
+  std::vector<int64_t> voff;                     // the current level's owner ranges
+  std::vector<std::vector<int64_t>> level_voff;  // every level's
+  int64_t edges0 = 0, ghosts0 = 0;               // the 1D partition's shape at level 0
+  mg_level L;
+  mg_sweep_view W;
+  dbuf<uint32_t> level_gh;  // the kept clustering of the ghosts (the rows' is the dendrogram level)
+  long long const* afix() const { return L.afix.data(); }
+  int const* pcnt() const { return L.pcnt.data(); }
+
+  void begin_level(louvain_state& S, level_graph& g, double const* k, uint8_t const* has_edges)
+  {
+    hipStream_t s = S.s;
+    L.nv = g.nv;
+    L.lo = g.base;
+    L.nr = g.nrows;
+    L.voff_d.resize(voff.size(), s);
+    to_device(L.voff_d.data(), voff.data(), voff.size(), s);
+    level_voff.push_back(voff);
+    mg_setup_level(S, g, L, has_edges, k);
+    if (level_voff.size() == 1) {
+      edges0  = g.ne;
+      ghosts0 = L.ng;
+    }
+    level_gh.resize(std::max<int64_t>(L.ng, 1), s);
+    if (L.ng)
+      HIP_CHECK(hipMemcpyAsync(level_gh.data(), L.c_gh.data(), L.ng * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  }
+  cluster_view view(louvain_state& S, bool all_present)
+  {
+    mg_view(S, L, all_present, W);
+    return {W.c_loc.data(), W.a.data(), W.present.data(), W.ncl};
+  }
+  void advance(louvain_state& S, dbuf<uint32_t>& next, uint8_t const* has_edges)
+  {
+    mg_advance(S, L, W, next.data(), has_edges);
+  }
+  void keep(louvain_state& S, uint32_t* level)
+  {
+    HIP_CHECK(hipMemcpyAsync(level, L.c_own.data(), L.nr * sizeof(uint32_t), hipMemcpyDeviceToDevice, S.s));
+    if (L.ng)
+      HIP_CHECK(hipMemcpyAsync(level_gh.data(), L.c_gh.data(), L.ng * sizeof(uint32_t), hipMemcpyDeviceToDevice, S.s));
+  }
+  void end_level() { W = mg_sweep_view{}; }
+  void release()
+  {
+    W = mg_sweep_view{};
+    L = mg_level{};
+    level_gh.free();
+  }
+  level_graph contract_level(louvain_state& S, level_graph const& g, uint32_t* level)
+  {
+    level_graph out = mg_contract(S, g, L, level, level_gh.data(), voff);
+    release();
+    return out;
+  }
+};
 
 template <typename V, typename E, typename R>
 void mg_louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolution, clustering_result_t& res)
@@ -2857,9 +2934,9 @@ void mg_louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolutio
   level_graph cur = mg_level0<V, R>(h, g);
   device_sum(plain_f{cur.w.data()}, (size_t)cur.ne, S.scal.data(), S.scratch.data(), s);
   comm.allreduce<double>(S.scal.data(), S.scal.data(), 1, CGX_COMM_SUM, s);
-  S.m = to_host_scalar(S.scal.data(), s);
-  {  // the owners' fixed-point cluster weights (scale 2^(60 - e), every |k| and cluster
-     // weight below the total 2^e) assume w >= 0: negative (or NaN) weights are refused
+  S.set_total_weight(to_host_scalar(S.scal.data(), s));
+  {  // the owners' fixed-point cluster weights (every |k| and cluster weight below the
+     // total) assume w >= 0: negative (or NaN) weights are refused
     dbuf<u64> st(2, s);
     fill<u64>(st.data(), 2, 0ull, s);
     if (cur.ne)
@@ -2870,111 +2947,13 @@ void mg_louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolutio
     CGX_EXPECTS(bad == 0, CUGRAPH_NOT_IMPLEMENTED, "multi-GPU Louvain: negative edge weights are not supported");
   }
 
-  bool const trace = std::getenv("CGX_LOUVAIN_TRACE") != nullptr;  // measurement only
-  // CGX_LOUVAIN_TRACE=2 (debugging only): every rank syncs and names each phase as it
-  // ends, so a rank that stops shows where
-  bool const phases = trace && std::atoi(std::getenv("CGX_LOUVAIN_TRACE")) >= 2;
-  auto phase        = [&](char const* what, size_t i) {
-    if (!phases) return;
-    HIP_CHECK(hipStreamSynchronize(s));
-    std::fprintf(stderr, "[louvain-mg r%d] %s %zu\n", p, what, i);
-  };
-  std::vector<int64_t> voff = mg.voff;
   std::vector<dbuf<uint32_t>> dendrogram;  // per level: the owned ids' clusters (coarse ids after contraction)
-  std::vector<std::vector<int64_t>> level_voff;
-  double best_q = -1.0;
-  size_t sweeps = 0, sweep_bytes = 0;
-  while (dendrogram.size() < max_level) {
-    mg_level L;
-    L.nv   = cur.nv;
-    L.lo   = cur.base;
-    L.nr   = cur.nrows;
-    L.voff = voff;
-    L.voff_d.resize(P + 1, s);
-    to_device(L.voff_d.data(), voff.data(), (size_t)P + 1, s);
-    int64_t const nr = L.nr, r1 = std::max<int64_t>(nr, 1);
-    level_voff.push_back(voff);
-    dbuf<int64_t> off(nr + 1, s);
-    lower_bounds(key_of<uint32_t>{cur.src.data()}, cur.ne, target_index{}, nr, off.data(), s);
-    dbuf<double> k(r1, s), self(r1, s);
-    dbuf<uint8_t> has_edges(r1, s);
-    // vertex weights on the global destinations (self loops: dst == row + base), then
-    // the destinations become local ids
-    dbuf<u64> vstats(2, s);
-    vertex_weights(S, cur, off.data(), k.data(), self.data(), has_edges.data(), vstats.data());
-    S.bytes = 0;
-    mg_setup_level(S, cur, L, has_edges.data(), k.data());
-    if (dendrogram.empty()) {  // the 1D partition's shape at level 0 (handle statistics)
-      h.last_louvain_local_edges = cur.ne;
-      h.last_louvain_ghosts      = L.ng;
-    }
-    phase("setup", dendrogram.size());
-    size_t const setup_bytes = S.bytes;
-    dendrogram.emplace_back(r1, s);
-    uint32_t* level = dendrogram.back().data();
-    dbuf<uint32_t> level_gh(std::max<int64_t>(L.ng, 1), s);
-    HIP_CHECK(hipMemcpyAsync(level, L.c_own.data(), nr * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    if (L.ng)
-      HIP_CHECK(hipMemcpyAsync(level_gh.data(), L.c_gh.data(), L.ng * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    sweep_plan plan;
-    plan_sweeps(S, cur, off.data(), vstats.data(), plan);
-    phase("plan", dendrogram.size());
-    dbuf<double> own(r1, s);
-    dbuf<uint32_t> next(r1, s);
-    mg_sweep_view W;
-    bool all_present = true;  // the first sweep: every cluster present (fill 1, as the single-GPU loop)
-    bool up_down     = true;  // as the single-GPU loop: sweep k + 1 before the decision on clustering k
-    S.bytes          = 0;
-    mg_view(S, L, all_present, W);
-    phase("view", sweeps);
-    sweep(S, cur, plan, W.c_loc.data(), next.data(), k.data(), self.data(), W.a.data(), W.present.data(), W.ncl, up_down,
-          own.data());
-    phase("sweep", sweeps);
-    double new_q = mg_modularity(S, L, own.data(), all_present);
-    ++sweeps;
-    sweep_bytes += S.bytes;
-    if (trace && p == 0)
-      std::fprintf(stderr, "[louvain-mg] level %zu nv=%lld setup %zu B/rank, sweep %zu B/rank q=%.6f\n",
-                   dendrogram.size() - 1, (long long)L.nv, setup_bytes, S.bytes, new_q);
-    double cur_q = new_q - 1.0;
-    while (new_q > cur_q + 0.0001) {
-      cur_q = new_q;
-      S.bytes = 0;
-      mg_advance(S, L, W, next.data(), has_edges.data());
-      phase("advance", sweeps);
-      all_present = false;
-      up_down     = !up_down;
-      mg_view(S, L, all_present, W);
-      phase("view", sweeps);
-      sweep(S, cur, plan, W.c_loc.data(), next.data(), k.data(), self.data(), W.a.data(), W.present.data(), W.ncl,
-            up_down,
-            own.data());
-      phase("sweep", sweeps);
-      new_q = mg_modularity(S, L, own.data(), all_present);
-      ++sweeps;
-      sweep_bytes += S.bytes;
-      if (trace && p == 0)
-        std::fprintf(stderr, "[louvain-mg]   sweep %zu B/rank (%lld referenced clusters) q=%.6f\n", S.bytes,
-                     (long long)W.ncl, new_q);
-      if (new_q > cur_q) {
-        HIP_CHECK(hipMemcpyAsync(level, L.c_own.data(), nr * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        if (L.ng)
-          HIP_CHECK(
-            hipMemcpyAsync(level_gh.data(), L.c_gh.data(), L.ng * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-      }
-    }
-    if (cur_q <= best_q) break;
-    best_q = cur_q;
-    // the level's sweep state goes before the contraction's sort buffers are allocated
-    plan = sweep_plan{};
-    W    = mg_sweep_view{};
-    for (auto* b : {&own, &k, &self}) b->free();
-    next.free();
-    has_edges.free();
-    off.free();
-    cur = mg_contract(S, cur, L, level, level_gh.data(), voff);
-    phase("contract", dendrogram.size());
-  }
+  mg_clusters C;
+  C.voff              = mg.voff;
+  double const best_q = run_levels(S, cur, max_level, C, dendrogram);
+  auto const& level_voff = C.level_voff;
+  h.last_louvain_local_edges = C.edges0;
+  h.last_louvain_ghosts      = C.ghosts0;
   // flatten_dendrogram for the owned level-0 vertices: level i's owners answer
   // for the ids the chain has reached
   dbuf<uint32_t> flat(std::max<int64_t>(n_own, 1), s);
@@ -3008,7 +2987,7 @@ void mg_louvain_impl(handle_t& h, graph_t& g, size_t max_level, double resolutio
   HIP_CHECK(hipStreamSynchronize(s));
   res.modularity             = best_q;
   h.last_louvain_levels      = dendrogram.size();
-  h.last_louvain_sweep_bytes = sweeps ? (double)sweep_bytes / (double)sweeps : 0.0;
+  h.last_louvain_sweep_bytes = S.sweeps ? (double)S.sweep_bytes / (double)S.sweeps : 0.0;
 }
 
 }  // namespace

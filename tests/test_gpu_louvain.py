@@ -164,7 +164,10 @@ def test_dendrogram_levels_compose_to_clusters():
 
 @pytest.mark.parametrize("renumber,opts", [(True, {}), (False, {}), (True, {"louvain_big_hash": 0}),
                                            (False, {"louvain_big_cap": 16}),
-                                           (False, {"louvain_big_maxdeg": 3000})])
+                                           (False, {"louvain_big_maxdeg": 3000}),
+                                           (True, {"louvain_big_maxdeg": 4530}),
+                                           (False, {"louvain_big_maxdeg": 4530}),
+                                           (False, {"louvain_big_maxdeg": 2048})])
 def test_hash_sweep_equals_sort_sweep(renumber, opts):
     """The LDS-hash local move (louvain.hip: k_sweep_hash for rows of <= 2048 edges,
     k_big_partials / k_big_buckets / k_big_move for heavier rows; fixed-point pair
@@ -174,13 +177,22 @@ def test_hash_sweep_equals_sort_sweep(renumber, opts):
     path inside the hash schedule (not a prefix of the rows without renumbering:
     gathered COO), and a (row, bucket) table cap of 16 that overflows, so the level
     falls back to the sort path for its heavy rows mid-sweep, and rows above 3000
-    edges on the sort path beside the LDS passes (the > 2.5M-edge rule).  (The 64-bit pair
-    keys of levels with >= 2^24 - 1 ids: test_hash_sweep_wide_keys, own process.)"""
+    edges on the sort path beside the LDS passes (the > 2.5M-edge rule).  This graph's 17
+    heavy level-0 rows have 4442 ... 4591 and 9645 edges, so the limit 3000 sends all of
+    them to the sort path at level 0; the limit 4530 lies between two of them (9 rows
+    taken, 8 not): with renumbering the rows not taken are a prefix of the
+    degree-ordered rows (their sort-path COO is the level's own), without it they
+    interleave with the taken ones (gathered COO), and the taken rows are indexed by
+    their rank among the taken.  The limit 2048 takes no heavy row at any level.  (The
+    64-bit pair keys of levels with >= 2^24 - 1 ids: test_hash_sweep_wide_keys, own
+    process.)"""
     s, d = rmat.rmat(16, 16 << 16, seed=11)
     w = np.floor(rmat.rmat_weights(s.size, seed=12).astype(np.float64) * 8.0) + 1.0
     s, d, w = og.symmetrize_dedup(s, d, w)
     deg = np.bincount(s)
     assert deg.max() > 2048 and deg[0] <= 2048  # hub rows exist, and row 0 is not one
+    heavy = deg[deg > 2048]
+    assert (heavy > 4530).any() and (heavy <= 4530).any()  # the limit 4530 splits the hub rows
     h, G = make_graph(s, d, w, renumber=renumber, symmetric=True, options=opts)
     v, c, q = run(h, G)
     lv = h.last_louvain_levels()
