@@ -74,6 +74,13 @@ struct tuning_t {
                                 // 1 every edge to a thread, 2 every edge to a wave (triangle_count.hip)
   int core_scan        = 0;     // core number: 0 a level's scan reads every vertex, 1 it reads the compacted list of
                                 // the vertices not yet peeled (core_number.hip; 0 measured faster)
+  int sim_path         = 0;     // similarity: 0 a pair goes to a thread, a wave or the split tier by its row sizes,
+                                // 1 every pair to a thread, 2 every pair to a wave, 3 every pair through the split
+                                // tier (similarity.hip)
+  int64_t sim_split_min = 4096; // similarity: a pair whose shorter row has at least this many entries is cut into
+                                // segments, a wave each (similarity.hip; at least 1)
+  int64_t two_hop_budget = (int64_t)1 << 26;  // two-hop neighbours: walks expanded and sorted per batch of source
+                                // rows; a row above it goes through a V-bit map (two_hop.hip; 2^26 measured)
 };
 
 struct handle_t {
@@ -259,6 +266,9 @@ struct adjacency_t {
   int64_t tc_edges = -1;  // oriented edges, -1 = not built yet
   buffer tc_ooff;         // edge_t[V + 1]
   buffer tc_oidx;         // vertex_t[tc_edges], ascending within each row (!degree_sorted only)
+  // Similarity (similarity.hip): distinct ids per row, built on the first call
+  bool sim_deg_valid = false;
+  buffer sim_deg;         // edge_t[V]
   pr_push_t pr;  // PageRank windowed-push schedule (pagerank.hip), built on first use
 };
 
@@ -311,6 +321,15 @@ struct k_core_result_t {  // reference c_api/core_result.hpp
   std::unique_ptr<device_array_t> src;
   std::unique_ptr<device_array_t> dst;
   std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
+};
+
+struct vertex_pairs_t {  // reference c_api/graph_helper / vertex_pairs.hpp
+  std::unique_ptr<device_array_t> first;
+  std::unique_ptr<device_array_t> second;
+};
+
+struct similarity_result_t {  // reference c_api/similarity.cpp
+  std::unique_ptr<device_array_t> similarity;  // weight type
 };
 
 struct paths_result_t {

@@ -568,6 +568,19 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value == 0 || value == 1, "Invalid input argument: core_scan must be 0 or 1");
       i32(t.core_scan);
     }
+    else if (n == "sim_path") {
+      CGX_INPUT(value == 0 || value == 1 || value == 2 || value == 3,
+                "Invalid input argument: sim_path must be 0, 1, 2 or 3");
+      i32(t.sim_path);
+    }
+    else if (n == "sim_split_min") {
+      CGX_INPUT(value >= 1, "Invalid input argument: sim_split_min must be at least 1");
+      t.sim_split_min = (int64_t)value;
+    }
+    else if (n == "two_hop_budget") {
+      CGX_INPUT(value >= 1, "Invalid input argument: two_hop_budget must be at least 1");
+      t.two_hop_budget = (int64_t)value;
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

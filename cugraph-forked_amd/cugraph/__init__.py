@@ -10,8 +10,9 @@ this image: edge lists are pandas DataFrames (or dicts of numpy arrays / torch
 tensors) and results come back as pandas DataFrames.
 """
 from .structure import DiGraph, Graph, from_edgelist, from_pandas_edgelist
-from .algorithms import (bfs, connected_components, core_number, eigenvector_centrality, hits, k_core, katz_centrality,
-                         louvain, pagerank, shortest_path, shortest_path_length, sssp,
+from .algorithms import (bfs, connected_components, core_number, eigenvector_centrality, hits, jaccard,
+                         jaccard_coefficient, k_core, katz_centrality, louvain, overlap, overlap_coefficient,
+                         pagerank, shortest_path, shortest_path_length, sorensen, sorensen_coefficient, sssp,
                          strongly_connected_components, triangle_count, weakly_connected_components)
 from . import generators
 from . import dask  # noqa: F401  (multi-GPU, one process per GPU)
@@ -19,4 +20,5 @@ from . import dask  # noqa: F401  (multi-GPU, one process per GPU)
 __all__ = ["Graph", "DiGraph", "from_edgelist", "from_pandas_edgelist", "pagerank", "bfs", "sssp",
            "shortest_path", "shortest_path_length", "louvain", "katz_centrality", "eigenvector_centrality", "hits",
            "weakly_connected_components", "strongly_connected_components", "connected_components",
-           "triangle_count", "core_number", "k_core", "generators", "dask"]
+           "triangle_count", "core_number", "k_core", "jaccard", "sorensen", "overlap", "jaccard_coefficient",
+           "sorensen_coefficient", "overlap_coefficient", "generators", "dask"]

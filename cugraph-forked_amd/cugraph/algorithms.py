@@ -432,6 +432,100 @@ def k_core(G, k=None, core_number=None):
     return out
 
 
+def _similarity(G, vertex_pair, measure):
+    """link_prediction/jaccard.py:21-134 and its siblings, for one of 'jaccard', 'sorensen',
+    'overlap'."""
+    import pandas as pd
+    import torch
+    if G.is_directed():
+        raise ValueError("Input must be an undirected Graph.")
+    if vertex_pair is not None and not isinstance(vertex_pair, pd.DataFrame):
+        raise ValueError("vertex_pair must be a cudf dataframe")
+    vt = _vertex_dtype(G)
+    if vertex_pair is None:  # the stored edges, both directions
+        e = G.edgelist
+        first, second = e["src"].cpu().numpy(), e["dst"].cpu().numpy()
+        order = np.lexsort((second, first))
+        first, second = first[order], second[order]
+    else:
+        if vertex_pair.shape[1] < 2:
+            raise ValueError("vertex_pair must have two columns")
+        first, second = vertex_pair.iloc[:, 0].to_numpy(), vertex_pair.iloc[:, 1].to_numpy()
+    p = _plc()
+    a = torch.as_tensor(np.ascontiguousarray(first)).to(vt).cuda()
+    b = torch.as_tensor(np.ascontiguousarray(second)).to(vt).cuda()
+    f = getattr(p, measure + "_coefficients")
+    a, b, score = f(p.ResourceHandle(), G._plc_graph, a, b, False, False)
+    return pd.DataFrame({"source": a.cpu().numpy(), "destination": b.cpu().numpy(),
+                         measure + "_coeff": score.cpu().numpy()})
+
+
+def _similarity_coefficient(G, ebunch, measure):
+    import pandas as pd
+    nxv = None
+    if _is_nx(G):
+        if G.is_directed():
+            raise ValueError("Input must be an undirected Graph.")
+        nxv = _NxView(G)
+        G = nxv.G
+    pairs = None
+    if ebunch is not None:
+        if isinstance(ebunch, pd.DataFrame):
+            pairs = ebunch
+        else:
+            ebunch = list(ebunch)
+            us, vs = [u for u, _ in ebunch], [v for _, v in ebunch]
+            if nxv is not None:
+                us, vs = nxv.ids(us), nxv.ids(vs)
+            pairs = pd.DataFrame({"first": np.asarray(us, dtype=np.int64), "second": np.asarray(vs, dtype=np.int64)})
+    df = _similarity(G, pairs, measure)
+    if nxv is not None:  # utilities/utils.py df_edge_score_to_dictionary
+        return dict(zip(zip(nxv.label(df["source"]), nxv.label(df["destination"])),
+                        df[measure + "_coeff"].tolist()))
+    return df
+
+
+def jaccard(input_graph, vertex_pair=None):
+    """link_prediction/jaccard.py:21-134.  Returns DataFrame ['source', 'destination',
+    'jaccard_coeff'], one row per pair in the order given: |N(u) & N(v)| / |N(u) | N(v)|, where
+    N(x) is the set of distinct neighbours in x's stored row (a self-loop makes x its own
+    neighbour).  ``vertex_pair`` is a DataFrame whose first two columns are the pairs; None means
+    the graph's stored edges, both directions, sorted by (source, destination).  Scores are exact:
+    the integer sizes in float64, rounded once to the graph's weight dtype (float32 without
+    weights); a zero denominator scores 0.  Undirected graphs only."""
+    return _similarity(input_graph, vertex_pair, "jaccard")
+
+
+def sorensen(input_graph, vertex_pair=None):
+    """link_prediction/sorensen.py.  As ``jaccard`` with column 'sorensen_coeff':
+    2 |N(u) & N(v)| / (|N(u)| + |N(v)|)."""
+    return _similarity(input_graph, vertex_pair, "sorensen")
+
+
+def overlap(input_graph, vertex_pair=None):
+    """link_prediction/overlap.py.  As ``jaccard`` with column 'overlap_coeff':
+    |N(u) & N(v)| / min(|N(u)|, |N(v)|)."""
+    return _similarity(input_graph, vertex_pair, "overlap")
+
+
+def jaccard_coefficient(G, ebunch=None):
+    """link_prediction/jaccard.py:137-190.  ``jaccard`` that also takes a NetworkX graph:
+    ``ebunch`` is then a list of node pairs (None: every edge, both directions) and the result a
+    dict {(u, v): score} in node labels.  For a Graph, ``ebunch`` may be a list of id pairs or a
+    DataFrame and the result is ``jaccard``'s DataFrame."""
+    return _similarity_coefficient(G, ebunch, "jaccard")
+
+
+def sorensen_coefficient(G, ebunch=None):
+    """link_prediction/sorensen.py.  See ``jaccard_coefficient``."""
+    return _similarity_coefficient(G, ebunch, "sorensen")
+
+
+def overlap_coefficient(G, ebunch=None):
+    """link_prediction/overlap.py.  See ``jaccard_coefficient``."""
+    return _similarity_coefficient(G, ebunch, "overlap")
+
+
 def _max_degree(G):
     import torch
     e = G.edgelist

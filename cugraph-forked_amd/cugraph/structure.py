@@ -230,6 +230,24 @@ class Graph:
         e = self.edgelist
         return bool(((e["src"] == n).any() | (e["dst"] == n).any()).item())
 
+    def get_two_hop_neighbors(self, start_vertices=None):
+        """simpleGraph.py get_two_hop_neighbors.  DataFrame ['first', 'second'] sorted by (first,
+        second): every ordered pair (u, v), u != v, joined by a walk of two out-edges, pairs that
+        are also adjacent included.  ``start_vertices`` (a list or Series of ids) restricts u."""
+        import pandas as pd
+        import torch
+        if self.is_distributed():
+            raise NotImplementedError("get_two_hop_neighbors of a distributed graph is not implemented in this build")
+        start = None
+        if start_vertices is not None:
+            if hasattr(start_vertices, "to_numpy"):
+                start_vertices = start_vertices.to_numpy()
+            start = torch.as_tensor(np.atleast_1d(np.asarray(start_vertices))).to(self.edgelist["src"].dtype).cuda()
+        first, second = _plc().get_two_hop_neighbors(self._handle, self._plc_graph, start)
+        first, second = first.cpu().numpy(), second.cpu().numpy()
+        order = np.lexsort((second, first))
+        return pd.DataFrame({"first": first[order], "second": second[order]})
+
     def to_undirected(self):
         G = Graph()
         import pandas as pd

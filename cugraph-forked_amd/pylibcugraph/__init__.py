@@ -7,8 +7,10 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 (personalized_pagerank.pyx), ``bfs`` (bfs.pyx:59-200), ``sssp`` (sssp.pyx:52-178),
 ``louvain`` (louvain.pyx:58-149), ``weakly_connected_components``
 (weakly_connected_components.pyx, components/_connectivity.pyx:132-220), ``triangle_count``
-(triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140) and ``k_core`` (the C
-entry of core_algorithms.h) -- same argument names, order, return tuples and
+(triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140), ``k_core`` (the C
+entry of core_algorithms.h), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
+``overlap_coefficients`` (jaccard_coefficients.pyx:58-150 and its siblings) and
+``get_two_hop_neighbors`` (the C entry of graph_functions.h) -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -26,7 +28,8 @@ from . import comms  # noqa: E402,F401  (multi-GPU communicator contexts)
 __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", "MGGraph", "pagerank",
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
-           "core_number", "k_core", "version"]
+           "core_number", "k_core", "jaccard_coefficients", "sorensen_coefficients", "overlap_coefficients",
+           "get_two_hop_neighbors", "version"]
 
 
 def allocator_stats():
@@ -544,3 +547,62 @@ def k_core(resource_handle, graph, k, degree_type, core_result, do_expensive_che
         ptrs.append(w)
     out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_k_core_result_free)
     return out[0], out[1], (out[2] if w else None)
+
+
+def _similarity(api, resource_handle, graph, first, second, use_weight, do_expensive_check):
+    h = resource_handle.ptr
+    a, b = DeviceView(first), DeviceView(second)
+    pairs = ctypes.c_void_p()
+    _lib.call("cugraph_create_vertex_pairs", h, graph.c_graph_ptr, a.ptr, b.ptr, ctypes.byref(pairs))
+    res = ctypes.c_void_p()
+    try:
+        _lib.call(api, h, graph.c_graph_ptr, pairs, int(bool(use_weight)), int(bool(do_expensive_check)),
+                  ctypes.byref(res))
+    finally:
+        _lib.lib.cugraph_vertex_pairs_free(pairs)
+    (score,) = views_to_tensors_owned(h, [_lib.lib.cugraph_similarity_result_get_similarity(res)], res,
+                                      _lib.lib.cugraph_similarity_result_free)
+    return a.tensor, b.tensor, score
+
+
+def jaccard_coefficients(resource_handle, graph, first, second, use_weight, do_expensive_check):
+    """jaccard_coefficients.pyx:58-150.  Returns (first, second, coefficients): for pair i =
+    (first[i], second[i]), |N(u) & N(v)| / |N(u) | N(v)|, where N(x) is the set of distinct ids in
+    x's stored row (a self-loop makes x a member, a repeated entry counts once).  Computed from the
+    integers in double and rounded once to the graph's weight type (float32 without weights); a zero
+    denominator scores 0.  ``first`` and ``second`` hold external ids in the graph's vertex type, in
+    any order, repeats and (u, u) allowed; an id that is not in the graph scores 0, or raises
+    ValueError with ``do_expensive_check``.  The graph must be symmetric; ``use_weight=True`` raises
+    NotImplementedError."""
+    return _similarity("cugraph_jaccard_coefficients", resource_handle, graph, first, second, use_weight,
+                       do_expensive_check)
+
+
+def sorensen_coefficients(resource_handle, graph, first, second, use_weight, do_expensive_check):
+    """sorensen_coefficients.pyx.  As ``jaccard_coefficients`` with the score
+    2 |N(u) & N(v)| / (|N(u)| + |N(v)|)."""
+    return _similarity("cugraph_sorensen_coefficients", resource_handle, graph, first, second, use_weight,
+                       do_expensive_check)
+
+
+def overlap_coefficients(resource_handle, graph, first, second, use_weight, do_expensive_check):
+    """overlap_coefficients.pyx.  As ``jaccard_coefficients`` with the score
+    |N(u) & N(v)| / min(|N(u)|, |N(v)|)."""
+    return _similarity("cugraph_overlap_coefficients", resource_handle, graph, first, second, use_weight,
+                       do_expensive_check)
+
+
+def get_two_hop_neighbors(resource_handle, graph, start_vertices=None):
+    """C entry cugraph_two_hop_neighbors (graph_functions.h).  Returns (first, second): every
+    ordered pair (u, v), u != v, with a walk u -> w -> v over the out-edges, each pair once, in
+    external ids; pairs that are also adjacent are included.  ``start_vertices``: None for every
+    vertex, or the ids u is restricted to (repeats do not repeat pairs; an id that is not in the
+    graph raises ValueError).  The order is unspecified but the same from call to call."""
+    h = resource_handle.ptr
+    start = optional_view(start_vertices)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_two_hop_neighbors", h, graph.c_graph_ptr, vptr(start), ctypes.byref(res))
+    first, second = views_to_tensors_owned(h, [_lib.lib.cugraph_vertex_pairs_get_first(res),
+                                               _lib.lib.cugraph_vertex_pairs_get_second(res)],
+                                           res, _lib.lib.cugraph_vertex_pairs_free)
+    return first, second

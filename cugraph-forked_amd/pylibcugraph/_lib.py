@@ -134,6 +134,16 @@ _proto("cugraph_k_core_result_get_src_vertices", P, P)
 _proto("cugraph_k_core_result_get_dst_vertices", P, P)
 _proto("cugraph_k_core_result_get_weights", P, P)
 _proto("cugraph_k_core_result_free", None, P)
+_proto("cugraph_create_vertex_pairs", c_int, P, P, P, P, PP, PP)
+_proto("cugraph_vertex_pairs_get_first", P, P)
+_proto("cugraph_vertex_pairs_get_second", P, P)
+_proto("cugraph_vertex_pairs_free", None, P)
+_proto("cugraph_two_hop_neighbors", c_int, P, P, P, PP, PP)
+_proto("cugraph_similarity_result_get_similarity", P, P)
+_proto("cugraph_similarity_result_free", None, P)
+_proto("cugraph_jaccard_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_sorensen_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_overlap_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
 _proto("cugraph_louvain", c_int, P, P, c_size_t, c_double, c_int, PP, PP)
 _proto("cugraph_heirarchical_clustering_result_get_vertices", P, P)
 _proto("cugraph_heirarchical_clustering_result_get_clusters", P, P)

@@ -127,7 +127,11 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * average degree), sssp_pull (0 by size | -1 never | n), wcc_sample (neighbours linked per vertex before
  * the giant component is guessed, 0: none), tc_path (triangle count: 0 thread or wave per oriented edge by
  * row size | 1 always a thread | 2 always a wave), core_scan (core number: 0 the scan of a level reads every
- * vertex | 1 it reads the compacted list of the vertices not yet peeled); "defaults" resets them all.  Booleans
+ * vertex | 1 it reads the compacted list of the vertices not yet peeled), sim_path (similarity: 0 a pair
+ * goes to a thread, a wave or the split tier by its row sizes | 1 always a thread | 2 always a wave | 3 always
+ * the split tier), sim_split_min (similarity: a pair whose shorter row has at least this many entries is cut
+ * into segments, a wave each; at least 1), two_hop_budget (two-hop neighbours: walks expanded and sorted per
+ * batch of source rows, a row above it goes through a V-bit map; at least 1); "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,

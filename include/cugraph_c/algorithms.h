@@ -9,6 +9,8 @@
 #include <cugraph_c/core_algorithms.h>
 #include <cugraph_c/error.h>
 #include <cugraph_c/graph.h>
+#include <cugraph_c/graph_functions.h>
 #include <cugraph_c/labeling_algorithms.h>
 #include <cugraph_c/resource_handle.h>
+#include <cugraph_c/similarity_algorithms.h>
 #include <cugraph_c/traversal_algorithms.h>

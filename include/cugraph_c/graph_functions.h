@@ -1,0 +1,66 @@
+/*
+ * libcugraph_c vertex pairs and two-hop neighbours -- MI355X build.
+ * ABI-compatible with the reference cpp/include/cugraph_c/graph_functions.h:27-100
+ * (implementation c_api/graph_functions.cpp, whose two-hop body the reference snapshot leaves
+ * unimplemented; algorithm traversal/two_hop_neighbors.cu).  Kernels: csrc/two_hop.hip.
+ */
+#pragma once
+#include <cugraph_c/array.h>
+#include <cugraph_c/error.h>
+#include <cugraph_c/graph.h>
+#include <cugraph_c/resource_handle.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* reference graph_functions.h:30-32 -- two arrays of vertex ids of one length, pair i = (first[i], second[i]) */
+typedef struct { int32_t align_; } cugraph_vertex_pairs_t;
+
+/*
+ * reference graph_functions.h:49-55.  Both views are copied, so the caller's arrays may go once the
+ * call returns.  The ids are external ids in the graph's vertex type, in any order; repeated pairs
+ * and pairs (u, u) are allowed, and an id that is not in the graph is accepted here (the similarity
+ * calls treat it as a vertex without neighbours).
+ * CUGRAPH_INVALID_INPUT: "vertex type of graph and first must match" / "... second ..." when a view's
+ * type differs from the graph's vertex type, and when the two views differ in length.
+ */
+cugraph_error_code_t cugraph_create_vertex_pairs(const cugraph_resource_handle_t* handle,
+                                                 cugraph_graph_t* graph,
+                                                 const cugraph_type_erased_device_array_view_t* first,
+                                                 const cugraph_type_erased_device_array_view_t* second,
+                                                 cugraph_vertex_pairs_t** vertex_pairs,
+                                                 cugraph_error_t** error);
+
+/* reference graph_functions.h:63 -- external ids, vertex type */
+cugraph_type_erased_device_array_view_t* cugraph_vertex_pairs_get_first(cugraph_vertex_pairs_t* vertex_pairs);
+
+/* reference graph_functions.h:72 */
+cugraph_type_erased_device_array_view_t* cugraph_vertex_pairs_get_second(cugraph_vertex_pairs_t* vertex_pairs);
+
+/* reference graph_functions.h:80 */
+void cugraph_vertex_pairs_free(cugraph_vertex_pairs_t* vertex_pairs);
+
+/*
+ * reference graph_functions.h:95-100.  Every ordered pair (u, v), u != v, for which the graph has
+ * a walk u -> w -> v over its out-edges, each pair once, in external ids.  A pair whose vertices
+ * are also adjacent is included (as in traversal/two_hop_neighbors.cu).  Works on any single-GPU
+ * graph, directed or not; a multi-GPU graph gives CUGRAPH_NOT_IMPLEMENTED.
+ *
+ * start_vertices: NULL for every vertex, or a list that restricts u (vertex type, external ids);
+ * repeating an id in it does not repeat pairs, and an id that is not in the graph is
+ * CUGRAPH_INVALID_INPUT.
+ *
+ * The order of the result is not specified, but it is the same from call to call (and for every
+ * value of the handle option two_hop_budget, which bounds the temporary memory: source rows are
+ * expanded in batches of at most that many walks).
+ */
+cugraph_error_code_t cugraph_two_hop_neighbors(const cugraph_resource_handle_t* handle,
+                                               const cugraph_graph_t* graph,
+                                               const cugraph_type_erased_device_array_view_t* start_vertices,
+                                               cugraph_vertex_pairs_t** result,
+                                               cugraph_error_t** error);
+
+#ifdef __cplusplus
+}
+#endif
