@@ -148,6 +148,57 @@ struct handle_t {
   }
 };
 
+// every algorithm call starts its statistics from zero
+inline void reset_hot(handle_t& h)
+{
+  h.last_iterations   = 0;
+  h.last_hot_ms       = 0;
+  h.last_hot_launches = 0;
+}
+
+// Profiling: pairs of pooled HIP events around the hot launches, summed into last_hot_ms.
+// One pair spans a whole chunk of launches (PageRank: an event between every two
+// iterations cost a ~10 us queue gap per iteration, and chunk time / iterations run is the
+// result, so the no-op launches after convergence in the last chunk count against the
+// kernels).  fold() adds the finished intervals to the total and hands their events back,
+// so a caller that folds after every chunk's host synchronisation (core number: one
+// interval per round) holds no more events than a chunk records.  With profiling off
+// nothing is recorded and nothing synchronises.
+struct chunk_timer {
+  handle_t& h;
+  hipStream_t s;
+  size_t live     = 0;  // events recorded since the last fold
+  double total_ms = 0;
+  void begin()
+  {
+    if (h.profiling) HIP_CHECK(hipEventRecord(h.event(live), s));
+  }
+  void end()
+  {
+    if (!h.profiling) return;
+    HIP_CHECK(hipEventRecord(h.event(live + 1), s));
+    live += 2;
+  }
+  void fold()
+  {
+    if (!live) return;
+    HIP_CHECK(hipEventSynchronize(h.event(live - 1)));  // returns at once after a host synchronisation
+    for (size_t i = 0; i < live; i += 2) {
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, h.event(i), h.event(i + 1)));
+      total_ms += ms;
+    }
+    live = 0;
+  }
+  void report(size_t launches)  // launches: what last_hot_launches counts for this algorithm
+  {
+    if (!h.profiling) return;
+    fold();
+    h.last_hot_ms       = total_ms;
+    h.last_hot_launches = launches;
+  }
+};
+
 struct array_view_t {  // reference c_api/array.hpp:30-35
   void* data           = nullptr;
   size_t size          = 0;

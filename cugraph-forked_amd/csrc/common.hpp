@@ -208,24 +208,26 @@ struct types3 {
 
 // Valid combinations follow cpp/include/cugraph/utilities/graph_traits.hpp:40-57:
 // vertex in {i32,i64}, edge in {i32,i64}, sizeof(vertex) <= sizeof(edge), weight in {f32,f64}.
+// dispatch_ve is for the algorithms that never read a weight: one instantiation per (vertex, edge) pair.
+template <typename F>
+decltype(auto) dispatch_ve(data_type_id_t v, data_type_id_t e, F&& f)
+{
+  if (v == INT32 && e == INT32) return f(types3<int32_t, int32_t, void>{});
+  if (v == INT32 && e == INT64) return f(types3<int32_t, int64_t, void>{});
+  if (v == INT64 && e == INT64) return f(types3<int64_t, int64_t, void>{});
+  fail(CUGRAPH_UNSUPPORTED_TYPE_COMBINATION, "unsupported vertex/edge type combination");
+}
+
 template <typename F>
 decltype(auto) dispatch_vew(data_type_id_t v, data_type_id_t e, data_type_id_t w, F&& f)
 {
   if (w != FLOAT32 && w != FLOAT64)
     fail(CUGRAPH_UNSUPPORTED_TYPE_COMBINATION, "weight type must be FLOAT32 or FLOAT64");
-  if (v == INT32 && e == INT32) {
-    if (w == FLOAT32) return f(types3<int32_t, int32_t, float>{});
-    return f(types3<int32_t, int32_t, double>{});
-  }
-  if (v == INT32 && e == INT64) {
-    if (w == FLOAT32) return f(types3<int32_t, int64_t, float>{});
-    return f(types3<int32_t, int64_t, double>{});
-  }
-  if (v == INT64 && e == INT64) {
-    if (w == FLOAT32) return f(types3<int64_t, int64_t, float>{});
-    return f(types3<int64_t, int64_t, double>{});
-  }
-  fail(CUGRAPH_UNSUPPORTED_TYPE_COMBINATION, "unsupported vertex/edge type combination");
+  return dispatch_ve(v, e, [&](auto t) -> decltype(auto) {
+    using T = decltype(t);
+    if (w == FLOAT32) return f(types3<typename T::vertex_t, typename T::edge_t, float>{});
+    return f(types3<typename T::vertex_t, typename T::edge_t, double>{});
+  });
 }
 
 }  // namespace cgx

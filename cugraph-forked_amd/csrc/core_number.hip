@@ -423,11 +423,9 @@ inline unsigned core_grid(int per_cu) { return (unsigned)(std::max(device_cu_cou
 template <typename V, typename E>
 void core_numbers(handle_t& h, graph_t& g, E delta, bool expensive, E* deg)
 {
-  hipStream_t s       = h.stream;
-  int64_t const nv    = g.num_vertices;
-  h.last_iterations   = 0;
-  h.last_hot_ms       = 0;
-  h.last_hot_launches = 0;
+  hipStream_t s    = h.stream;
+  int64_t const nv = g.num_vertices;
+  reset_hot(h);
   if (nv == 0) return;
   if (g.num_edges == 0) {
     HIP_CHECK(hipMemsetAsync(deg, 0, (size_t)nv * sizeof(E), s));
@@ -478,37 +476,28 @@ void core_numbers(handle_t& h, graph_t& g, E delta, bool expensive, E* deg)
   // every round peels a vertex or is the one empty scan round before a round that does
   unsigned long long const round_cap = 2ull * (unsigned long long)nv + 4ull;
   size_t launches = 0;
-  double hot_ms   = 0;
+  chunk_timer timer{h, s};  // one interval per round, folded after every chunk's read
   while (true) {
     for (int r = 0; r < kCoreChunkRounds; ++r) {
       hipLaunchKernelGGL((k_core_scan<V, E>), dim3(grid), dim3(kCoreBlock), 0, s, a);
-      if (h.profiling) HIP_CHECK(hipEventRecord(h.event(2 * r), s));
+      timer.begin();
       hipLaunchKernelGGL((k_core_peel<V, E>), dim3(grid), dim3(kCoreBlock), 0, s, a);
       hipLaunchKernelGGL((k_core_peel_waves<V, E>), dim3(grid), dim3(kCoreBlock), 0, s, a);
       hipLaunchKernelGGL((k_core_peel_hubs<V, E>), dim3(hub_grid), dim3(kCoreBlock), 0, s, a);
-      if (h.profiling) HIP_CHECK(hipEventRecord(h.event(2 * r + 1), s));
+      timer.end();
       hipLaunchKernelGGL(k_core_ctl<E>, dim3(1), dim3(1), 0, s, st.data());
       CGX_LAUNCH_CHECK();
     }
     launches += 3 * (size_t)kCoreChunkRounds;
     HIP_CHECK(hipMemcpyAsync(hs, st.data(), sizeof(core_state<E>), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (h.profiling) {
-      for (int r = 0; r < kCoreChunkRounds; ++r) {
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, h.event(2 * r), h.event(2 * r + 1)));
-        hot_ms += ms;
-      }
-    }
+    timer.fold();
     CGX_EXPECTS(!hs->bad, CUGRAPH_UNKNOWN_ERROR, "core_number: a vertex list overflowed");
     if (hs->done) break;
     CGX_EXPECTS(hs->rounds <= round_cap, CUGRAPH_UNKNOWN_ERROR, "core_number: more rounds than vertices allow");
   }
   h.last_iterations = (size_t)hs->rounds;
-  if (h.profiling) {
-    h.last_hot_ms       = hot_ms;
-    h.last_hot_launches = launches;
-  }
+  timer.report(launches);
 }
 
 // ---------------------------------------------------------------- k-core
@@ -613,18 +602,14 @@ void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const
     CGX_INPUT(given->core_numbers->type == g.edge_type, "edge type of graph and core_result core_numbers must match");
   }
   if (nv == 0 || g.num_edges == 0) {
-    h.last_iterations = 0;
-    h.last_hot_ms = 0;
-    h.last_hot_launches = 0;
+    reset_hot(h);
     empty();
     return;
   }
   adjacency_t& adj = ensure_adjacency(h, g, g.store_transposed);  // symmetric: either orientation
   cn.resize((size_t)nv, s);
   if (given) {
-    h.last_iterations = 0;
-    h.last_hot_ms = 0;
-    h.last_hot_launches = 0;
+    reset_hot(h);
     size_t const n = given->vertices->size;
     HIP_CHECK(hipMemsetAsync(cn.data(), 0, (size_t)nv * sizeof(E), s));  // not listed: core 0
     if (n) {
@@ -675,7 +660,7 @@ void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const
 // delta: 1 (K_CORE_DEGREE_TYPE_IN / _OUT) or 2 (_INOUT)
 void run_core_number(handle_t& h, graph_t& g, int delta, bool expensive, core_result_t& res)
 {
-  dispatch_vew(g.vertex_type, g.edge_type, g.weight_type, [&](auto t) {
+  dispatch_ve(g.vertex_type, g.edge_type, [&](auto t) {
     using T = decltype(t);
     using V = typename T::vertex_t;
     using E = typename T::edge_t;

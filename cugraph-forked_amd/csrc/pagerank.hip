@@ -2747,39 +2747,6 @@ inline void check_alpha_eps(double alpha, double eps)
   CGX_INPUT(eps >= 0.0, "Invalid input argument: epsilon should be non-negative.");
 }
 
-// Profiling: one pair of pooled HIP events around each chunk of iterations -- an event
-// between every two iterations cost a ~10 us queue gap per iteration -- and chunk time /
-// iterations run as the result, so the no-op launches after convergence in the last chunk
-// count against the kernels.
-struct chunk_timer {
-  handle_t& h;
-  hipStream_t s;
-  std::vector<hipEvent_t> ev;
-  void begin()
-  {
-    if (!h.profiling) return;
-    ev.push_back(h.event(ev.size()));  // pooled on the handle
-    ev.push_back(h.event(ev.size()));
-    HIP_CHECK(hipEventRecord(ev[ev.size() - 2], s));
-  }
-  void end()
-  {
-    if (h.profiling) HIP_CHECK(hipEventRecord(ev.back(), s));
-  }
-  void report(int iters)  // after the last chunk's host synchronisation
-  {
-    if (!h.profiling) return;
-    double tot = 0;
-    for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      tot += ms;
-    }
-    h.last_hot_ms       = tot;
-    h.last_hot_launches = std::max<size_t>((size_t)iters, 1);
-  }
-};
-
 template <typename V, typename E, typename R>
 void set_queue_args(push_args<V, E, R>& sa, pr_push_t& pp, hipStream_t s)
 {
@@ -2863,9 +2830,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   int64_t nv = g.num_vertices;
   res.vertices = number_map_copy(h, g);
   res.values   = std::make_unique<device_array_t>((size_t)nv, dtype_of<R>(), s);
-  h.last_iterations = 0;
-  h.last_hot_ms     = 0;
-  h.last_hot_launches = 0;
+  reset_hot(h);
   if (nv == 0) return;
 
   adjacency_t& adj = ensure_adjacency(h, g, /*transposed=*/true);
@@ -3010,7 +2975,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   }
   // Chunked enqueue (next_chunk): a host check after 8 iterations, then after the
   // predicted remainder; profiling times the chunks (chunk_timer)
-  chunk_timer timer{h, s, {}};
+  chunk_timer timer{h, s};
   pr_state hst{};
   R* bufs[2]    = {xa.data(), xb.data()};
   size_t launched = 0;
@@ -3079,7 +3044,7 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
       std::fclose(f);
     }
   }
-  timer.report(hst.iter);
+  timer.report(std::max<size_t>((size_t)hst.iter, 1));
   if (hst.done == 2) fail(CUGRAPH_UNKNOWN_ERROR, "PageRank failed to converge.");
 }
 
@@ -3376,9 +3341,7 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
     HIP_CHECK(hipMemcpyAsync(res.vertices->buf.data(), g.number_map.data(), n_own * sizeof(V), hipMemcpyDeviceToDevice,
                              s));
   res.values = std::make_unique<device_array_t>((size_t)n_own, dtype_of<R>(), s);
-  h.last_iterations   = 0;
-  h.last_hot_ms       = 0;
-  h.last_hot_launches = 0;
+  reset_hot(h);
   if (g.num_vertices == 0) return;
   mg_pr_block& blk = mg_block<V, E, R>(h, g);
   int const C = mg.C, R_ = mg.R;
@@ -3514,7 +3477,7 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
   }
 
   size_t launched = 0;
-  chunk_timer timer{h, s, {}};
+  chunk_timer timer{h, s};
   pr_state hst{};
   pr_state* hpin = h.pinned_as<pr_state>();
   {
@@ -3572,7 +3535,7 @@ void mg_pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_
     }
   }
   h.last_iterations = (size_t)hst.iter;
-  timer.report(hst.iter);
+  timer.report(std::max<size_t>((size_t)hst.iter, 1));
   if (hst.done == 2) fail(CUGRAPH_UNKNOWN_ERROR, "PageRank failed to converge.");
 }
 

@@ -173,6 +173,25 @@ void to_device(T* dev, T const* host, size_t n, hipStream_t s)
   if (n) HIP_CHECK(hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, s));
 }
 
+// internal ids after renumber_ext_to_int_unchecked: an id that is not in the graph is -1 or out of range
+template <typename V>
+__global__ void k_bad_ids(V const* a, V const* b, size_t n, int64_t nv, int* bad)
+{
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    if (a[i] < 0 || (int64_t)a[i] >= nv || (b && (b[i] < 0 || (int64_t)b[i] >= nv))) atomicOr(bad, 1);
+}
+// CUGRAPH_INVALID_INPUT with `msg` unless every id of a[0, n) (and of b, when given) lies in [0, nv);
+// one host read
+template <typename V>
+void expect_ids_in_range(V const* a, V const* b, size_t n, int64_t nv, char const* msg, hipStream_t s)
+{
+  dbuf<int> bad(1, s);
+  HIP_CHECK(hipMemsetAsync(bad.data(), 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_bad_ids<V>, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, a, b, n, nv, bad.data());
+  CGX_LAUNCH_CHECK();
+  CGX_INPUT(to_host_scalar(bad.data(), s) == 0, msg);
+}
+
 template <typename T>
 __global__ void k_minmax(T const* a, size_t n, long long* mn, long long* mx)
 {

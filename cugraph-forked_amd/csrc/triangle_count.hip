@@ -21,9 +21,10 @@
 //
 // Counting (one launch, no host read): a thread takes one oriented edge (u, v), found by a
 // search of its index in ooff.  Short rows are merged by the thread; an edge with a row of
-// kTcWaveLen entries or more is handed to the wave, whose lanes look the shorter row's
+// kIsectWaveLen entries or more is handed to the wave, whose lanes look the shorter row's
 // entries up in the longer one by binary search, in the wave's LDS slice when it fits and
-// pays.  A hub row is many work items, so it is spread over as many blocks as its size
+// pays (intersect.hpp holds the merge, the probe and the staging; tc_sink is what this file
+// passes as their `hit`).  A hub row is many work items, so it is spread over as many blocks as its size
 // asks for.  Per triangle only the third vertex costs an atomic; the edge's own count goes
 // to v once per edge and to u once per run of lanes that share u.  Repeated entries of a
 // row are skipped on both sides, so they neither add nor multiply triangles.
@@ -31,25 +32,16 @@
 // of a power-law graph, are summed in the block's LDS and flushed once per block.
 // Counts are summed in 64 bits with device-scope atomics and read by the next launch.
 #include "capi.hpp"
+#include "intersect.hpp"
 #include "prims.hpp"
 
 namespace cgx {
 
 namespace {
 
-constexpr int kTcBlock      = 256;
-constexpr int kTcWaveLen    = 64;    // an edge with a row of at least this many entries: the wave
-constexpr int kTcStageBytes = 4096;  // LDS slice of a wave (1024 4-byte ids), 16 KiB per block
-constexpr int kTcHubs       = 2048;  // degree-sorted: third-vertex hits on ids below this are summed in LDS (16 KiB)
-constexpr int kTcGridPerCu  = 8;     // blocks per CU of the count launch; each flushes its hub sums once
-constexpr int kTcStageDiv   = 64;    // stage the longer row when the shorter has at least 1/64 of its entries
-
-using count_t = unsigned long long;
-
-__device__ __forceinline__ void bump(count_t* p, count_t c)
-{
-  __hip_atomic_fetch_add(p, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+constexpr int kTcBlock     = kIsectBlock;
+constexpr int kTcHubs      = 2048;  // degree-sorted: third-vertex hits on ids below this are summed in LDS (16 KiB)
+constexpr int kTcGridPerCu = 8;     // blocks per CU of the count launch; each flushes its hub sums once
 
 // Where a triangle's third vertex is counted.  Third vertices are the highest-ranked ones, so on a
 // power-law graph nearly all hits land on a few hub counters (R-MAT-20: one of them takes 7.5 M of
@@ -59,7 +51,7 @@ struct tc_sink {
   count_t* hub;  // LDS, kTcHubs entries
   long long hubs;
   template <typename V>
-  __device__ __forceinline__ void hit(V w) const
+  __device__ __forceinline__ void operator()(V w) const  // the `hit` of intersect.hpp
   {
     if ((long long)w < hubs) __hip_atomic_fetch_add(hub + w, (count_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     else bump(cnt + w, 1);
@@ -114,64 +106,18 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_rank_rows(E const* off, V const
 }
 
 // ---------------------------------------------------------------- counting
-// a thread merges two short rows; runs of equal ids count once
-template <typename V>
-__device__ __forceinline__ count_t tc_merge(V const* A, long long na, V const* B, long long nb, tc_sink const& out)
-{
-  count_t c     = 0;
-  long long i = 0, j = 0;
-  while (i < na && j < nb) {
-    V const x = A[i], y = B[j];
-    if (x < y) ++i;
-    else if (y < x) ++j;
-    else {
-      out.hit(x);
-      ++c;
-      do ++i; while (i < na && A[i] == x);
-      do ++j; while (j < nb && B[j] == x);
-    }
-  }
-  return c;
-}
-
-// the lanes of a wave look the entries of S up in L (global memory or the wave's LDS slice);
-// returns this lane's hits
-template <typename V, typename P>
-__device__ __forceinline__ count_t tc_probe(V const* S, long long ns, P L, long long nl, int lane,
-                                            tc_sink const& out)
-{
-  count_t c = 0;
-  for (long long i = lane; i < ns; i += 64) {
-    V const x = S[i];
-    if (i > 0 && S[i - 1] == x) continue;  // a repeated entry
-    long long lo = 0, hi = nl;
-    while (lo < hi) {
-      long long const mid = (lo + hi) >> 1;
-      if (L[mid] < x) lo = mid + 1;
-      else hi = mid;
-    }
-    if (lo < nl && L[lo] == x) {
-      out.hit(x);
-      ++c;
-    }
-  }
-  return c;
-}
-
 // One oriented edge per thread and 256-edge chunk.  path: tuning_t::tc_path; hubs: kTcHubs when the
 // ids are the ranks, else 0.
 template <typename V, typename E>
 __global__ __launch_bounds__(kTcBlock) void k_tc_count(E const* base, E const* ooff, V const* idx, int64_t nv,
                                                       int path, int hubs, count_t* cnt)
 {
-  constexpr int kStage = kTcStageBytes / (int)sizeof(V);
-  __shared__ V stage_all[(kTcBlock / 64) * kStage];
   __shared__ count_t hub[kTcHubs];
   int const tid = threadIdx.x, lane = tid & 63;
   for (int i = tid; i < hubs; i += kTcBlock) hub[i] = 0;
   __syncthreads();
   tc_sink const out{cnt, hub, (long long)hubs};
-  V* const stage     = stage_all + (tid >> 6) * kStage;
+  V* const stage     = isect_stage<V>();
   long long const ne = (long long)ooff[nv];
   for (long long k0 = blockIdx.x * (long long)kTcBlock; k0 < ne; k0 += (long long)gridDim.x * kTcBlock) {
     long long const k = k0 + tid;
@@ -198,10 +144,10 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_count(E const* base, E const* o
       }
     }
     bool const work    = lb > 0;  // la >= 1 whenever there is an edge
-    bool const by_wave = work && (path == 2 || (path == 0 && (la >= kTcWaveLen || lb >= kTcWaveLen)));
+    bool const by_wave = work && (path == 2 || (path == 0 && (la >= kIsectWaveLen || lb >= kIsectWaveLen)));
     count_t c          = 0;
     if (work && !by_wave) {
-      c = tc_merge<V>(idx + a0, la, idx + b0, lb, out);
+      c = isect_merge<V>(idx + a0, la, idx + b0, lb, out);
       if (c) bump(cnt + v, c);
     }
     // u's share: consecutive edges share u, so the lanes of a run add up first
@@ -224,26 +170,8 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_count(E const* base, E const* o
       long long const uu = __shfl(u, l, 64), vv = __shfl(v, l, 64);
       long long sa = __shfl(a0, l, 64), ns = __shfl(la, l, 64);
       long long sb = __shfl(b0, l, 64), nl = __shfl(lb, l, 64);
-      if (ns > nl) {  // S: the shorter row, L: the longer
-        long long t = sa; sa = sb; sb = t;
-        t = ns; ns = nl; nl = t;
-      }
-      V const* S = idx + sa;
-      V const* L = idx + sb;
-      count_t cw;
-      if (nl <= kStage && ns * kTcStageDiv >= nl) {
-        // DS operations of one wave complete in order; the barriers only pin the compiler
-        __builtin_amdgcn_wave_barrier();
-        for (long long j = lane; j < nl; j += 64) stage[j] = L[j];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        cw = tc_probe<V, V const*>(S, ns, stage, nl, lane, out);
-        __builtin_amdgcn_wave_barrier();
-      } else {
-        cw = tc_probe<V, V const*>(S, ns, L, nl, lane, out);
-      }
-      cw = (count_t)wave_sum_ll((long long)cw);
+      isect_shorter_first(sa, ns, sb, nl);
+      count_t const cw = isect_wave_count<V>(idx + sa, 0, ns, idx + sb, nl, stage, kIsectStageDiv, lane, out);
       if (lane == 0 && cw) {
         bump(cnt + uu, cw);
         bump(cnt + vv, cw);
@@ -267,13 +195,6 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_finish(count_t const* cnt, int6
     if (sizeof(E) == 4 && c > (count_t)INT32_MAX) atomicOr(flag, 1);
     counts[i] = (E)c;
   }
-}
-
-template <typename V>
-__global__ __launch_bounds__(kTcBlock) void k_tc_bad_ids(V const* ids, size_t n, int64_t nv, int* bad)
-{
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    if (ids[i] < 0 || (int64_t)ids[i] >= nv) atomicOr(bad, 1);
 }
 
 // Builds the oriented rows of `adj` once (the only host read: their total).
@@ -317,10 +238,8 @@ void tc_impl(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
 {
   hipStream_t s       = h.stream;
   int64_t const nv    = g.num_vertices;
-  h.last_iterations   = 0;
-  h.last_hot_ms       = 0;
-  h.last_hot_launches = 0;
-  size_t n            = (size_t)nv;
+  reset_hot(h);
+  size_t n = (size_t)nv;
   dbuf<V> ids;  // internal ids of the start list
   if (start) {
     n            = start->size;
@@ -330,14 +249,9 @@ void tc_impl(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
       HIP_CHECK(hipMemcpyAsync(res.vertices->buf.data(), start->data, n * sizeof(V), hipMemcpyDefault, s));
       HIP_CHECK(hipMemcpyAsync(ids.data(), start->data, n * sizeof(V), hipMemcpyDefault, s));
       renumber_ext_to_int_unchecked(h, g, ids.data(), n);  // ids not in the graph become -1
-      if (expensive) {  // triangle_count_impl.cuh:169-187
-        dbuf<int> bad(1, s);
-        HIP_CHECK(hipMemsetAsync(bad.data(), 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_tc_bad_ids<V>, dim3(grid_for(n, kTcBlock, 4096)), dim3(kTcBlock), 0, s, ids.data(), n, nv,
-                           bad.data());
-        CGX_LAUNCH_CHECK();
-        CGX_INPUT(to_host_scalar(bad.data(), s) == 0, "Invalid input arguments: invalid vertex IDs in *vertices.");
-      }
+      if (expensive)  // triangle_count_impl.cuh:169-187
+        expect_ids_in_range<V>(ids.data(), nullptr, n, nv, "Invalid input arguments: invalid vertex IDs in *vertices.",
+                               s);
     }
   } else {
     res.vertices = number_map_copy(h, g);
@@ -360,12 +274,8 @@ void tc_impl(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
   dbuf<int> flag(1, s);
   HIP_CHECK(hipMemsetAsync(cnt.data(), 0, (size_t)nv * sizeof(count_t), s));
   HIP_CHECK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h.profiling) {
-    e0 = h.event(0);
-    e1 = h.event(1);
-    HIP_CHECK(hipEventRecord(e0, s));
-  }
+  chunk_timer timer{h, s};
+  timer.begin();
   size_t launches = 1;
   if (adj.tc_edges > 0) {
     int const hubs = adj.degree_sorted ? (int)std::min<int64_t>(nv, kTcHubs) : 0;
@@ -379,14 +289,8 @@ void tc_impl(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
                      (count_t const*)cnt.data(), nv, start ? (V const*)ids.data() : (V const*)nullptr, n, counts,
                      flag.data());
   CGX_LAUNCH_CHECK();
-  if (h.profiling) {
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    h.last_hot_ms       = ms;
-    h.last_hot_launches = launches;
-  }
+  timer.end();
+  timer.report(launches);
   if (sizeof(E) == 4)  // the one read of the call, after the last launch
     CGX_EXPECTS(to_host_scalar(flag.data(), s) == 0, CUGRAPH_UNSUPPORTED_TYPE_COMBINATION,
                 "triangle_count: a vertex's count does not fit the graph's 32-bit edge type; "
@@ -398,7 +302,7 @@ void tc_impl(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
 void run_triangle_count(handle_t& h, graph_t& g, array_view_t const* start, bool expensive,
                         triangle_count_result_t& res)
 {
-  dispatch_vew(g.vertex_type, g.edge_type, g.weight_type, [&](auto t) {
+  dispatch_ve(g.vertex_type, g.edge_type, [&](auto t) {
     using T = decltype(t);
     tc_impl<typename T::vertex_t, typename T::edge_t>(h, g, start, expensive, res);
   });

@@ -324,10 +324,10 @@ void two_hop_impl(handle_t& h, graph_t& g, array_view_t const* start, vertex_pai
 
 void run_two_hop(handle_t& h, graph_t& g, array_view_t const* start, vertex_pairs_t& res)
 {
-  if (g.vertex_type == INT32 && g.edge_type == INT32) two_hop_impl<int32_t, int32_t>(h, g, start, res);
-  else if (g.vertex_type == INT32 && g.edge_type == INT64) two_hop_impl<int32_t, int64_t>(h, g, start, res);
-  else if (g.vertex_type == INT64 && g.edge_type == INT64) two_hop_impl<int64_t, int64_t>(h, g, start, res);
-  else fail(CUGRAPH_UNSUPPORTED_TYPE_COMBINATION, "unsupported vertex/edge type combination");
+  dispatch_ve(g.vertex_type, g.edge_type, [&](auto t) {
+    using T = decltype(t);
+    two_hop_impl<typename T::vertex_t, typename T::edge_t>(h, g, start, res);
+  });
 }
 
 }  // namespace cgx

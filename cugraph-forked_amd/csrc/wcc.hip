@@ -210,9 +210,7 @@ void wcc_impl(handle_t& h, graph_t& g, labeling_result_t& res)
   int64_t const nv  = g.num_vertices;
   res.vertices      = number_map_copy(h, g);
   res.labels        = std::make_unique<device_array_t>((size_t)nv, g.vertex_type, s);
-  h.last_iterations   = 0;
-  h.last_hot_ms       = 0;
-  h.last_hot_launches = 0;
+  reset_hot(h);
   if (nv == 0) return;
   // symmetric: either orientation is the same adjacency
   adjacency_t& adj = ensure_adjacency(h, g, g.store_transposed);
@@ -245,12 +243,8 @@ void wcc_impl(handle_t& h, graph_t& g, labeling_result_t& res)
   dbuf<unsigned> hub_count(1, s);
   HIP_CHECK(hipMemsetAsync(hub_count.data(), 0, sizeof(unsigned), s));
 
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h.profiling) {
-    e0 = h.event(0);
-    e1 = h.event(1);
-    HIP_CHECK(hipEventRecord(e0, s));
-  }
+  chunk_timer timer{h, s};
+  timer.begin();
   for (int r = 0; r < k; ++r) {
     hipLaunchKernelGGL((k_wcc_sample<V, E>), dim3(grid), dim3(kWccBlock), 0, s, off, idx, nv, r, parent);
     hipLaunchKernelGGL(k_wcc_compress<V>, dim3(grid), dim3(kWccBlock), 0, s, nv, parent);
@@ -270,14 +264,8 @@ void wcc_impl(handle_t& h, graph_t& g, labeling_result_t& res)
   CGX_LAUNCH_CHECK();
   launches += 3;
   h.last_iterations = (size_t)k;
-  if (h.profiling) {
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    h.last_hot_ms       = ms;
-    h.last_hot_launches = launches;
-  }
+  timer.end();
+  timer.report(launches);
 }
 
 }  // namespace
@@ -285,7 +273,7 @@ void wcc_impl(handle_t& h, graph_t& g, labeling_result_t& res)
 void run_wcc(handle_t& h, graph_t& g, bool expensive, labeling_result_t& res)
 {
   (void)expensive;  // weakly_connected_components_impl.cuh:289-291: nothing to check
-  dispatch_vew(g.vertex_type, g.edge_type, g.weight_type, [&](auto t) {
+  dispatch_ve(g.vertex_type, g.edge_type, [&](auto t) {
     using T = decltype(t);
     wcc_impl<typename T::vertex_t, typename T::edge_t>(h, g, res);
   });
