@@ -81,6 +81,10 @@ struct tuning_t {
                                 // segments, a wave each (similarity.hip; at least 1)
   int64_t two_hop_budget = (int64_t)1 << 26;  // two-hop neighbours: walks expanded and sorted per batch of source
                                 // rows; a row above it goes through a V-bit map (two_hop.hip; 2^26 measured)
+  uint64_t sample_seed = 0;     // neighbour sampling and random walks: the seed of sample.hpp's draw (below 2^53; the
+                                // reference's ABI has no seed argument and its C API passes 0)
+  int sample_path      = 0;     // neighbour sampling without replacement: 0 a slot's Floyd sampler goes to a thread or
+                                // a wave by the fan-out, 1 always a thread, 2 always a wave (sampling.hip)
 };
 
 struct handle_t {
@@ -320,6 +324,10 @@ struct adjacency_t {
   // Similarity (similarity.hip): distinct ids per row, built on the first call
   bool sim_deg_valid = false;
   buffer sim_deg;         // edge_t[V]
+  // Biased random walks (random_walks.hip): every row's inclusive prefix sum of its weights, in double, added
+  // left to right; built on the first call
+  bool cum_valid = false;
+  buffer cum;             // double[E]
   pr_push_t pr;  // PageRank windowed-push schedule (pagerank.hip), built on first use
 };
 
@@ -381,6 +389,22 @@ struct vertex_pairs_t {  // reference c_api/graph_helper / vertex_pairs.hpp
 
 struct similarity_result_t {  // reference c_api/similarity.cpp
   std::unique_ptr<device_array_t> similarity;  // weight type
+};
+
+struct sample_result_t {  // reference c_api/uniform_neighbor_sampling.cpp:31-38
+  std::unique_ptr<device_array_t> src;
+  std::unique_ptr<device_array_t> dst;
+  std::unique_ptr<device_array_t> index;   // weight type: the edges' weight bits, ones without weights
+  std::unique_ptr<device_array_t> counts;  // edge type: how often each triple was drawn (cugraph_amd_sample_result_get_counts)
+  // cugraph_test_sample_result_create only: the counts it was given, on the host, for the reference's
+  // host-view getter; a sample call leaves it null and that getter returns NULL
+  std::unique_ptr<host_array_t> given_counts;
+};
+
+struct random_walk_result_t {  // reference c_api/random_walks.cpp:34-40
+  size_t max_length = 0;
+  std::unique_ptr<device_array_t> paths;    // vertex type [n x (max_length + 1)], row major, -1 after a sink
+  std::unique_ptr<device_array_t> weights;  // weight type [n x max_length]; null for an unweighted graph
 };
 
 struct paths_result_t {

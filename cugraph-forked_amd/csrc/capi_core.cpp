@@ -581,6 +581,15 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value >= 1, "Invalid input argument: two_hop_budget must be at least 1");
       t.two_hop_budget = (int64_t)value;
     }
+    else if (n == "sample_seed") {
+      CGX_INPUT(value >= 0 && value < 9007199254740992.0 && value == (double)(uint64_t)value,
+                "Invalid input argument: sample_seed must be an integer in [0, 2^53)");
+      t.sample_seed = (uint64_t)value;
+    }
+    else if (n == "sample_path") {
+      CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: sample_path must be 0, 1 or 2");
+      i32(t.sample_path);
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

@@ -9,19 +9,12 @@
 //   the reference): one 64-bit (src << b | dst) radix sort, run-head flags, scan, scatter.
 #include "capi.hpp"
 #include "prims.hpp"
+#include "sample.hpp"  // splitmix64
 
 #include <cugraph_amd/ext.h>
 
 namespace cgx {
 namespace {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ uint64_t scramble(uint64_t v, int scale, uint64_t seed)
 {

@@ -12,8 +12,9 @@ tensors) and results come back as pandas DataFrames.
 from .structure import DiGraph, Graph, from_edgelist, from_pandas_edgelist
 from .algorithms import (bfs, connected_components, core_number, eigenvector_centrality, hits, jaccard,
                          jaccard_coefficient, k_core, katz_centrality, louvain, overlap, overlap_coefficient,
-                         pagerank, shortest_path, shortest_path_length, sorensen, sorensen_coefficient, sssp,
-                         strongly_connected_components, triangle_count, weakly_connected_components)
+                         pagerank, random_walks, shortest_path, shortest_path_length, sorensen, sorensen_coefficient,
+                         sssp, strongly_connected_components, triangle_count, uniform_neighbor_sample,
+                         weakly_connected_components)
 from . import generators
 from . import dask  # noqa: F401  (multi-GPU, one process per GPU)
 
@@ -21,4 +22,5 @@ __all__ = ["Graph", "DiGraph", "from_edgelist", "from_pandas_edgelist", "pageran
            "shortest_path", "shortest_path_length", "louvain", "katz_centrality", "eigenvector_centrality", "hits",
            "weakly_connected_components", "strongly_connected_components", "connected_components",
            "triangle_count", "core_number", "k_core", "jaccard", "sorensen", "overlap", "jaccard_coefficient",
-           "sorensen_coefficient", "overlap_coefficient", "generators", "dask"]
+           "sorensen_coefficient", "overlap_coefficient", "uniform_neighbor_sample", "random_walks", "generators",
+           "dask"]

@@ -526,6 +526,77 @@ def overlap_coefficient(G, ebunch=None):
     return _similarity_coefficient(G, ebunch, "overlap")
 
 
+def uniform_neighbor_sample(G, start_list, fanout_vals, with_replacement=True, is_edge_ids=False):
+    """sampling/uniform_neighbor_sample.py:23-120.  Returns DataFrame ['sources', 'destinations',
+    'indices']: the distinct edges drawn when every vertex of ``start_list`` (an int, a list or a Series;
+    duplicates are sampled separately) picks ``fanout_vals[0]`` of its out-edges, their destinations pick
+    ``fanout_vals[1]`` each, and so on; a fan-out <= 0 takes every out-edge.  'indices' is the edge's
+    weight (1.0 for a graph without weights), cast back to int32 / int64 when the graph's edge list
+    carried such values (edge ids).  ``is_edge_ids`` is accepted and unused, as in the reference.  The
+    sample is the same on every call (pylibcugraph.uniform_neighbor_sample)."""
+    import pandas as pd
+    import torch
+    if isinstance(start_list, (int, np.integer)) and not isinstance(start_list, bool):
+        start_list = [start_list]
+    if isinstance(fanout_vals, list):
+        fanout_vals = np.asarray(fanout_vals, dtype="int32")
+    else:
+        raise TypeError(f"fanout_vals must be a list, got: {type(fanout_vals)}")
+    if hasattr(start_list, "to_numpy"):
+        start_list = start_list.to_numpy()
+    start = torch.as_tensor(np.atleast_1d(np.asarray(start_list))).to(_vertex_dtype(G)).cuda()
+    p = _plc()
+    sources, destinations, indices = p.uniform_neighbor_sample(p.ResourceHandle(), G._plc_graph, start, fanout_vals,
+                                                               bool(with_replacement), False)
+    indices = indices.cpu().numpy()
+    weight_t = getattr(G, "_weight_dtype", None)
+    if weight_t in (np.dtype(np.int32), np.dtype(np.int64)):
+        indices = indices.astype(weight_t)
+    return pd.DataFrame({"sources": sources.cpu().numpy(), "destinations": destinations.cpu().numpy(),
+                         "indices": indices})
+
+
+def random_walks(G, start_vertices, max_depth=None, use_padding=False):
+    """sampling/random_walks.py:19-104.  Uniform random walks of at most ``max_depth`` vertices from every
+    vertex of ``start_vertices`` (an int, a list or a Series).  Returns (vertex_paths, edge_weight_paths,
+    sizes) as pandas Series; sizes[i] is the number of vertices of walk i, which stops early at a vertex
+    without out-edges.  ``use_padding=True``: every walk takes max_depth vertex entries (-1 after its end)
+    and max_depth - 1 weight entries (0 after its end); otherwise the walks are coalesced, walk i taking
+    sizes[i] vertices and sizes[i] - 1 weights.  A graph without weights gives weights of 1."""
+    import pandas as pd
+    import torch
+    if max_depth is None:
+        raise TypeError("must specify a 'max_depth'")
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    if isinstance(start_vertices, (int, np.integer)) and not isinstance(start_vertices, bool):
+        start_vertices = [start_vertices]
+    if hasattr(start_vertices, "to_numpy"):
+        start_vertices = start_vertices.to_numpy()
+    if nxv is not None:
+        start_vertices = nxv.ids(list(start_vertices))
+    if int(max_depth) < 1:
+        raise ValueError(f"'max_depth' must be a positive integer, got: {max_depth}")
+    length = int(max_depth) - 1  # max_depth counts vertices, the C entry counts edges
+    start = torch.as_tensor(np.atleast_1d(np.asarray(start_vertices))).to(_vertex_dtype(G)).cuda()
+    p = _plc()
+    paths, weights, _ = p.uniform_random_walks(p.ResourceHandle(), G._plc_graph, start, length)
+    n = start.numel()
+    paths = paths.cpu().numpy().reshape(n, length + 1)
+    sizes = (paths >= 0).sum(axis=1).astype(np.int64)
+    steps = np.arange(length)[None, :] < (sizes - 1)[:, None]
+    weights = steps.astype(np.float32) if weights is None else weights.cpu().numpy().reshape(n, length)
+    if use_padding:
+        vertex_paths, edge_weight_paths = paths.reshape(-1), weights.reshape(-1)
+    else:
+        vertex_paths, edge_weight_paths = paths[paths >= 0], weights[steps]
+    if nxv is not None:
+        vertex_paths = np.asarray(nxv.label(vertex_paths), dtype=object)
+    return pd.Series(vertex_paths), pd.Series(edge_weight_paths), pd.Series(sizes)
+
+
 def _max_degree(G):
     import torch
     e = G.edgelist

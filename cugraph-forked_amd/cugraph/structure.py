@@ -79,6 +79,8 @@ class Graph:
         w = None
         if edge_attr is not None:
             w = _column(input_df, edge_attr)
+            # what the column held before the cast (uniform_neighbor_sample casts int32 / int64 edge ids back)
+            self._weight_dtype = {torch.int32: np.dtype(np.int32), torch.int64: np.dtype(np.int64)}.get(w.dtype)
             if w.dtype not in (torch.float32, torch.float64):
                 w = w.to(torch.float32)
             self.graph_properties.weights = True

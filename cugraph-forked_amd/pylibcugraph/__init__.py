@@ -10,7 +10,9 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 (triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140), ``k_core`` (the C
 entry of core_algorithms.h), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
 ``overlap_coefficients`` (jaccard_coefficients.pyx:58-150 and its siblings) and
-``get_two_hop_neighbors`` (the C entry of graph_functions.h) -- same argument names, order, return tuples and
+``get_two_hop_neighbors`` (the C entry of graph_functions.h), ``uniform_neighbor_sample``
+(uniform_neighbor_sample.pyx), ``uniform_random_walks`` / ``biased_random_walks`` (uniform_random_walks.pyx) and
+the ``node2vec`` stub -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -19,7 +21,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from ._arrays import (DeviceArray, DeviceView, copy_view_to_tensor, copy_views_to_tensors, optional_view,
+from ._arrays import (_NP_TO_C, DeviceArray, DeviceView, copy_view_to_tensor, copy_views_to_tensors, optional_view,
                       to_device_tensor, views_to_tensors_owned, vptr)
 
 from . import generators  # noqa: E402,F401  (MI355X build extensions)
@@ -29,7 +31,8 @@ __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", 
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
            "core_number", "k_core", "jaccard_coefficients", "sorensen_coefficients", "overlap_coefficients",
-           "get_two_hop_neighbors", "version"]
+           "get_two_hop_neighbors", "uniform_neighbor_sample", "uniform_random_walks", "biased_random_walks",
+           "node2vec", "version"]
 
 
 def allocator_stats():
@@ -606,3 +609,75 @@ def get_two_hop_neighbors(resource_handle, graph, start_vertices=None):
                                                _lib.lib.cugraph_vertex_pairs_get_second(res)],
                                            res, _lib.lib.cugraph_vertex_pairs_free)
     return first, second
+
+
+def uniform_neighbor_sample(resource_handle, input_graph, start_list, h_fan_out, with_replacement,
+                            do_expensive_check, return_counts=False):
+    """uniform_neighbor_sample.pyx:60-170.  Returns (sources, destinations, indices): the distinct edges
+    drawn over all hops, in no particular order; ``indices`` has the graph's weight type and carries each
+    edge's weight bit for bit (ones for a graph without weights).  ``start_list`` holds external ids in the
+    graph's vertex type, duplicates being slots of their own; ``h_fan_out`` is a non-empty host array of
+    int32, one fan-out per hop, a value <= 0 taking every out-edge.  The sample is a pure function of the
+    handle option ``sample_seed`` (default 0), the call's arguments and the graph
+    (include/cugraph_c/sampling_algorithms.h).  ``return_counts=True`` (MI355X build extension) appends how
+    often each edge was drawn."""
+    import numpy as np
+    h = resource_handle.ptr
+    start = DeviceView(start_list)
+    fan = np.ascontiguousarray(h_fan_out)
+    if fan.dtype not in _NP_TO_C:
+        raise TypeError(f"unsupported fan-out dtype {fan.dtype}")
+    fview = _lib.lib.cugraph_type_erased_host_array_view_create(fan.ctypes.data_as(ctypes.c_void_p), fan.size,
+                                                               _NP_TO_C[fan.dtype])
+    res = ctypes.c_void_p()
+    try:
+        _lib.call("cugraph_uniform_neighbor_sample", h, input_graph.c_graph_ptr, start.ptr, fview,
+                  int(bool(with_replacement)), int(bool(do_expensive_check)), ctypes.byref(res))
+    finally:
+        _lib.lib.cugraph_type_erased_host_array_view_free(fview)
+    ptrs = [_lib.lib.cugraph_sample_result_get_sources(res), _lib.lib.cugraph_sample_result_get_destinations(res),
+            _lib.lib.cugraph_sample_result_get_index(res)]
+    if return_counts:
+        ptrs.append(_lib.lib.cugraph_amd_sample_result_get_counts(res))
+    return tuple(views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_sample_result_free))
+
+
+def _random_walks(api, resource_handle, input_graph, start_vertices, max_length):
+    h = resource_handle.ptr
+    start = DeviceView(start_vertices)
+    res = ctypes.c_void_p()
+    _lib.call(api, h, input_graph.c_graph_ptr, start.ptr, int(max_length), ctypes.byref(res))
+    length = int(_lib.lib.cugraph_random_walk_result_get_max_path_length(res))
+    ptrs = [_lib.lib.cugraph_random_walk_result_get_paths(res)]
+    w = _lib.lib.cugraph_random_walk_result_get_weights(res)
+    if w:
+        ptrs.append(w)
+    out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_random_walk_result_free)
+    return out[0], (out[1] if w else None), length
+
+
+def uniform_random_walks(resource_handle, input_graph, start_vertices, max_length):
+    """uniform_random_walks.pyx:50-120.  Returns (paths, weights, max_length): ``paths`` is
+    [len(start_vertices) x (max_length + 1)] flattened row by row, external ids, each row starting with its
+    start vertex; ``weights`` is [len(start_vertices) x max_length] in the graph's weight type, None for a
+    graph without weights.  After a vertex without out-edges a row holds -1 and its weights 0.  Every step
+    picks an out-edge uniformly; the walks are a pure function of the handle option ``sample_seed``, the
+    start list and the graph."""
+    return _random_walks("cugraph_uniform_random_walks", resource_handle, input_graph, start_vertices, max_length)
+
+
+def biased_random_walks(resource_handle, input_graph, start_vertices, max_length):
+    """C entry cugraph_biased_random_walks.  As ``uniform_random_walks`` with every step picking an out-edge
+    with probability weight / sum of the row's weights; a row whose weights sum to 0 ends the walk.  The
+    graph must have weights and none may be negative (ValueError)."""
+    return _random_walks("cugraph_biased_random_walks", resource_handle, input_graph, start_vertices, max_length)
+
+
+def node2vec(resource_handle, graph, seed_array, max_depth, compress_result, p, q):
+    """node2vec.pyx:55-140.  Raises NotImplementedError through the C call: the node2vec biases are not
+    implemented in this build."""
+    start = DeviceView(seed_array)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_node2vec", resource_handle.ptr, graph.c_graph_ptr, start.ptr, int(max_depth),
+              int(bool(compress_result)), float(p), float(q), ctypes.byref(res))
+    raise NotImplementedError("node2vec is not implemented in this build")

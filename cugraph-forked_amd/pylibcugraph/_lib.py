@@ -144,6 +144,29 @@ _proto("cugraph_similarity_result_free", None, P)
 _proto("cugraph_jaccard_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
 _proto("cugraph_sorensen_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
 _proto("cugraph_overlap_coefficients", c_int, P, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_type_erased_host_array_view_create", P, P, c_size_t, c_int)
+_proto("cugraph_type_erased_host_array_view_free", None, P)
+_proto("cugraph_uniform_neighbor_sample", c_int, P, P, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_sample_result_get_sources", P, P)
+_proto("cugraph_sample_result_get_destinations", P, P)
+_proto("cugraph_sample_result_get_index", P, P)
+_proto("cugraph_amd_sample_result_get_counts", P, P)
+_proto("cugraph_sample_result_get_start_labels", P, P)
+_proto("cugraph_sample_result_get_counts", P, P)
+_proto("cugraph_sample_result_free", None, P)
+_proto("cugraph_test_sample_result_create", c_int, P, P, P, P, P, PP, PP)
+_proto("cugraph_type_erased_host_array_size", c_size_t, P)
+_proto("cugraph_type_erased_host_array_type", c_int, P)
+_proto("cugraph_type_erased_host_array_pointer", P, P)
+_proto("cugraph_uniform_random_walks", c_int, P, P, P, c_size_t, PP, PP)
+_proto("cugraph_biased_random_walks", c_int, P, P, P, c_size_t, PP, PP)
+_proto("cugraph_node2vec_random_walks", c_int, P, P, P, c_size_t, c_double, c_double, PP, PP)
+_proto("cugraph_node2vec", c_int, P, P, P, c_size_t, c_int, c_double, c_double, PP, PP)
+_proto("cugraph_random_walk_result_get_max_path_length", c_size_t, P)
+_proto("cugraph_random_walk_result_get_paths", P, P)
+_proto("cugraph_random_walk_result_get_weights", P, P)
+_proto("cugraph_random_walk_result_get_path_sizes", P, P)
+_proto("cugraph_random_walk_result_free", None, P)
 _proto("cugraph_louvain", c_int, P, P, c_size_t, c_double, c_int, PP, PP)
 _proto("cugraph_heirarchical_clustering_result_get_vertices", P, P)
 _proto("cugraph_heirarchical_clustering_result_get_clusters", P, P)

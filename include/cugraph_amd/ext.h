@@ -131,7 +131,11 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * goes to a thread, a wave or the split tier by its row sizes | 1 always a thread | 2 always a wave | 3 always
  * the split tier), sim_split_min (similarity: a pair whose shorter row has at least this many entries is cut
  * into segments, a wave each; at least 1), two_hop_budget (two-hop neighbours: walks expanded and sorted per
- * batch of source rows, a row above it goes through a V-bit map; at least 1); "defaults" resets them all.  Booleans
+ * batch of source rows, a row above it goes through a V-bit map; at least 1), sample_seed (neighbour sampling and
+ * random walks: the seed of the draw defined in cugraph_c/sampling_algorithms.h, an integer in [0, 2^53), default
+ * 0; the one of these options that changes a result), sample_path (neighbour sampling without replacement: 0 the
+ * Floyd sampler of a slot goes to a thread or a wave by the fan-out | 1 always a thread | 2 always a wave; the
+ * sample is the same under all three); "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,
@@ -168,6 +172,13 @@ void cugraph_amd_last_louvain_partition(const cugraph_resource_handle_t* handle,
 size_t cugraph_amd_heirarchical_clustering_result_get_num_levels(cugraph_heirarchical_clustering_result_t* result);
 cugraph_type_erased_device_array_view_t* cugraph_amd_heirarchical_clustering_result_get_level(
   cugraph_heirarchical_clustering_result_t* result, size_t level);
+
+/* Neighbour sampling: how often each returned (source, destination, index) triple was drawn, a device array
+ * of the graph's edge type aligned with cugraph_sample_result_get_sources.  The reference computes these
+ * counts and offers no working getter for them (its cugraph_sample_result_get_counts is never set on this
+ * path).  For a result of cugraph_test_sample_result_create: the counts it was given.  The view is freed
+ * by the caller and lives as long as the result. */
+cugraph_type_erased_device_array_view_t* cugraph_amd_sample_result_get_counts(const cugraph_sample_result_t* result);
 
 /* Return every cached HBM block of libcugraph_c's caching allocator to the driver
  * (synchronises the device).  Returns the bytes released.  The reference's

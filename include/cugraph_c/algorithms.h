@@ -12,5 +12,6 @@
 #include <cugraph_c/graph_functions.h>
 #include <cugraph_c/labeling_algorithms.h>
 #include <cugraph_c/resource_handle.h>
+#include <cugraph_c/sampling_algorithms.h>
 #include <cugraph_c/similarity_algorithms.h>
 #include <cugraph_c/traversal_algorithms.h>
