@@ -85,6 +85,10 @@ struct tuning_t {
                                 // reference's ABI has no seed argument and its C API passes 0)
   int sample_path      = 0;     // neighbour sampling without replacement: 0 a slot's Floyd sampler goes to a thread or
                                 // a wave by the fan-out, 1 always a thread, 2 always a wave (sampling.hip)
+  int bc_batch         = 64;    // betweenness: sources per batch, one per lane of a wave (1 .. 64; halved while the
+                                // V x batch x 20 bytes of state do not fit; betweenness.hip)
+  int64_t bc_row_split = 2048;  // betweenness: a row above this many entries is cut into segments of that many, a
+                                // wave each (a multiple of 64, the block of a row's sum: the cut changes no bit)
 };
 
 struct handle_t {
@@ -359,6 +363,12 @@ struct graph_t {
 struct centrality_result_t {
   std::unique_ptr<device_array_t> vertices;
   std::unique_ptr<device_array_t> values;
+};
+
+struct edge_centrality_result_t {  // edge betweenness: one entry per stored edge, in out-edge order
+  std::unique_ptr<device_array_t> src;
+  std::unique_ptr<device_array_t> dst;
+  std::unique_ptr<device_array_t> values;  // FLOAT64
 };
 
 struct labeling_result_t {  // reference c_api/labeling_result.hpp

@@ -35,6 +35,8 @@ void run_triangle_count(handle_t& h, graph_t& g, array_view_t const* start, bool
 void run_core_number(handle_t& h, graph_t& g, int delta, bool expensive, core_result_t& res);
 void run_k_core(handle_t& h, graph_t& g, size_t k, int delta, core_result_t const* given, bool expensive,
                 k_core_result_t& res);
+void run_betweenness(handle_t& h, graph_t& g, array_view_t const* vertex_list, bool normalized, bool endpoints,
+                     centrality_result_t* vres, edge_centrality_result_t* eres);
 void mg_run_pagerank(handle_t& h, graph_t& g, array_view_t const* pow_v, array_view_t const* pow_s,
                      array_view_t const* guess_v, array_view_t const* guess_s, array_view_t const* pers_v,
                      array_view_t const* pers_s, double alpha, double eps, size_t max_iter, bool expensive,
@@ -575,6 +577,93 @@ extern "C" cugraph_error_code_t cugraph_eigenvector_centrality(const cugraph_res
     HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
     *result = reinterpret_cast<cugraph_centrality_result_t*>(res.release());
   });
+}
+
+// ---------------------------------------------------------------- betweenness / edge betweenness
+// (names and argument order of later cuGraph releases' centrality_algorithms.h; the scores and their scaling
+// are centrality/betweenness_centrality.cu's; betweenness.hip)
+namespace {
+
+graph_t& betweenness_checks(const cugraph_resource_handle_t* handle, cugraph_graph_t* graph,
+                            const cugraph_type_erased_device_array_view_t* vertex_list, char const* multi_gpu_message)
+{
+  CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+  CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+  auto& g = *G(graph);
+  CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED, multi_gpu_message);
+  CGX_INPUT(!vertex_list || AV(vertex_list)->type == g.vertex_type, "vertex type of graph and vertex_list must match");
+  return g;
+}
+
+}  // namespace
+
+extern "C" cugraph_error_code_t cugraph_betweenness_centrality(const cugraph_resource_handle_t* handle,
+                                                              cugraph_graph_t* graph,
+                                                              const cugraph_type_erased_device_array_view_t* vertex_list,
+                                                              bool_t normalized,
+                                                              bool_t include_endpoints,
+                                                              bool_t do_expensive_check,
+                                                              cugraph_centrality_result_t** result,
+                                                              cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    auto& g = betweenness_checks(handle, graph, vertex_list,
+                                 "multi-GPU betweenness centrality is not implemented in this build");
+    (void)do_expensive_check;  // the one check there is, that every source is in the graph, is always made
+    auto res = std::make_unique<centrality_result_t>();
+    run_betweenness(*H(handle), g, vertex_list ? AV(vertex_list) : nullptr, normalized == TRUE,
+                    include_endpoints == TRUE, res.get(), nullptr);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_centrality_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_error_code_t cugraph_edge_betweenness_centrality(
+  const cugraph_resource_handle_t* handle,
+  cugraph_graph_t* graph,
+  const cugraph_type_erased_device_array_view_t* vertex_list,
+  bool_t normalized,
+  bool_t do_expensive_check,
+  cugraph_edge_centrality_result_t** result,
+  cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  return guarded(error, [&] {
+    auto& g = betweenness_checks(handle, graph, vertex_list,
+                                 "multi-GPU betweenness centrality (edge scores) is not implemented in this build");
+    (void)do_expensive_check;
+    auto res = std::make_unique<edge_centrality_result_t>();
+    run_betweenness(*H(handle), g, vertex_list ? AV(vertex_list) : nullptr, normalized == TRUE, false, nullptr,
+                    res.get());
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_edge_centrality_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_src_vertices(
+  cugraph_edge_centrality_result_t* result)
+{
+  return new_view(reinterpret_cast<edge_centrality_result_t*>(result)->src.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_dst_vertices(
+  cugraph_edge_centrality_result_t* result)
+{
+  return new_view(reinterpret_cast<edge_centrality_result_t*>(result)->dst.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_values(
+  cugraph_edge_centrality_result_t* result)
+{
+  return new_view(reinterpret_cast<edge_centrality_result_t*>(result)->values.get());
+}
+
+extern "C" void cugraph_edge_centrality_result_free(cugraph_edge_centrality_result_t* result)
+{
+  delete reinterpret_cast<edge_centrality_result_t*>(result);
 }
 
 extern "C" cugraph_error_code_t cugraph_hits(const cugraph_resource_handle_t* handle,

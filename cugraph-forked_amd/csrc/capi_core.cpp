@@ -590,6 +590,18 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: sample_path must be 0, 1 or 2");
       i32(t.sample_path);
     }
+    else if (n == "bc_batch") {
+      CGX_INPUT(value >= 1 && value <= 64 && value == (double)(int)value,
+                "Invalid input argument: bc_batch must be an integer in [1, 64]");
+      i32(t.bc_batch);
+    }
+    else if (n == "bc_row_split") {
+      // a multiple of 64: a row is summed in blocks of 64 entries, and a cut between blocks changes no bit
+      CGX_INPUT(value >= 64 && value <= 4611686018427387904.0 && value == (double)(int64_t)value &&
+                  (int64_t)value % 64 == 0,
+                "Invalid input argument: bc_row_split must be a multiple of 64, at least 64");
+      t.bc_row_split = (int64_t)value;
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

@@ -650,6 +650,66 @@ def eigenvector_centrality(G, max_iter=100, tol=1.0e-6):
     return df
 
 
+def _betweenness_setup(G, k, weight, result_dtype, what):
+    """The checks of centrality/betweenness_centrality.py:120-131 and its ``_initialize_vertices``:
+    returns (NetworkX view or None, Graph, k for pylibcugraph)."""
+    if weight is not None:
+        raise NotImplementedError(f"weighted implementation of {what} centrality not currently supported")
+    if result_dtype not in [np.float32, np.float64]:
+        raise TypeError("result type can only be np.float32 or np.float64")
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    if k is not None and not (isinstance(k, (int, np.integer)) and not isinstance(k, bool)):
+        # a list of identifiers (any sequence): the sources themselves
+        ids = nxv.ids(list(k)) if nxv is not None else list(np.asarray(k).tolist())
+        if any(not isinstance(i, (int, np.integer)) for i in ids):
+            raise ValueError("A provided vertex was not valid")
+        k = ids
+    return nxv, G, k
+
+
+def betweenness_centrality(G, k=None, normalized=True, weight=None, endpoints=False, seed=None,
+                           result_dtype=np.float64):
+    """centrality/betweenness_centrality.py:26-144.  Returns DataFrame ['vertex', 'betweenness_centrality']
+    (dict {node: score} for a NetworkX input).  ``k``: None (every vertex is a source), an int (that many
+    sources drawn with ``random.Random(seed)`` from the vertices' positions) or a list of vertex
+    identifiers.  Weights of G are ignored; ``weight`` is not supported, ``endpoints`` is."""
+    import pandas as pd
+    nxv, G, k = _betweenness_setup(G, k, weight, result_dtype, "betweenness")
+    p = _plc()
+    vertex, values = p.betweenness_centrality(p.ResourceHandle(), G._plc_graph, k, seed, normalized, endpoints, False)
+    df = pd.DataFrame({"vertex": vertex.cpu().numpy(),
+                       "betweenness_centrality": values.cpu().numpy().astype(result_dtype)})
+    if nxv is not None:
+        return dict(zip(nxv.label(df["vertex"]), df["betweenness_centrality"]))
+    return df
+
+
+def edge_betweenness_centrality(G, k=None, normalized=True, weight=None, seed=None, result_dtype=np.float64):
+    """centrality/betweenness_centrality.py:147-276.  Returns DataFrame ['src', 'dst',
+    'betweenness_centrality'] (dict {(u, v): score} for a NetworkX input).  For an undirected graph the
+    two directions of an edge are folded as the reference does (:260-271): swapped so that src < dst and
+    summed, one row per edge.  ``k`` as in ``betweenness_centrality``."""
+    import pandas as pd
+    nxv, G, k = _betweenness_setup(G, k, weight, result_dtype, "edge betweenness")
+    p = _plc()
+    src, dst, values = p.edge_betweenness_centrality(p.ResourceHandle(), G._plc_graph, k, seed, normalized, False)
+    df = pd.DataFrame({"src": src.cpu().numpy(), "dst": dst.cpu().numpy(),
+                       "betweenness_centrality": values.cpu().numpy()})
+    if not G.is_directed():
+        lower = (df["src"] >= df["dst"]).to_numpy()
+        s, d = df["src"].to_numpy().copy(), df["dst"].to_numpy().copy()
+        s[lower], d[lower] = df["dst"].to_numpy()[lower], df["src"].to_numpy()[lower]
+        df["src"], df["dst"] = s, d
+        df = df.groupby(by=["src", "dst"]).sum().reset_index()
+    df["betweenness_centrality"] = df["betweenness_centrality"].to_numpy().astype(result_dtype)
+    if nxv is not None:
+        return {(a, b): x for a, b, x in zip(nxv.label(df["src"]), nxv.label(df["dst"]), df["betweenness_centrality"])}
+    return df
+
+
 def hits(G, max_iter=100, tol=1.0e-5, nstart=None, normalized=True):
     """link_analysis/hits.py:26-120.  Returns DataFrame ['vertex', 'hubs', 'authorities']
     ((hubs dict, authorities dict) for a NetworkX input)."""

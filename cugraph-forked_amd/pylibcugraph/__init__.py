@@ -12,7 +12,8 @@ entry of core_algorithms.h), ``jaccard_coefficients`` / ``sorensen_coefficients`
 ``overlap_coefficients`` (jaccard_coefficients.pyx:58-150 and its siblings) and
 ``get_two_hop_neighbors`` (the C entry of graph_functions.h), ``uniform_neighbor_sample``
 (uniform_neighbor_sample.pyx), ``uniform_random_walks`` / ``biased_random_walks`` (uniform_random_walks.pyx) and
-the ``node2vec`` stub -- same argument names, order, return tuples and
+the ``node2vec`` stub, ``betweenness_centrality`` / ``edge_betweenness_centrality`` (the signatures of
+later pylibcugraph releases; 22.10 has none) -- same argument names, order, return tuples and
 exception types.  Arrays come back as GPU torch tensors (the reference returns
 cupy arrays).
 """
@@ -28,7 +29,8 @@ from . import generators  # noqa: E402,F401  (MI355X build extensions)
 from . import comms  # noqa: E402,F401  (multi-GPU communicator contexts)
 
 __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", "MGGraph", "pagerank",
-           "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "hits", "bfs", "sssp",
+           "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "betweenness_centrality",
+           "edge_betweenness_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
            "core_number", "k_core", "jaccard_coefficients", "sorensen_coefficients", "overlap_coefficients",
            "get_two_hop_neighbors", "uniform_neighbor_sample", "uniform_random_walks", "biased_random_walks",
@@ -209,6 +211,7 @@ class SGGraph(_GPUGraph):
                   int(bool(do_expensive_check)), ctypes.byref(g))
         self.c_graph_ptr = g.value
         self._mg = False
+        self._vertex_dtype = src.tensor.dtype
 
     def __del__(self, _sd=_lib.SHUTDOWN, _free=_lib.lib.cugraph_sg_graph_free):
         if getattr(self, "c_graph_ptr", None) and not _sd[0]:
@@ -235,6 +238,7 @@ class MGGraph(_GPUGraph):
                   int(bool(do_expensive_check)), ctypes.byref(g))
         self.c_graph_ptr = g.value
         self._mg = True
+        self._vertex_dtype = src.tensor.dtype
 
     def __del__(self, _sd=_lib.SHUTDOWN, _free=_lib.lib.cugraph_mg_graph_free):
         if getattr(self, "c_graph_ptr", None) and not _sd[0]:
@@ -299,6 +303,57 @@ def eigenvector_centrality(resource_handle, graph, epsilon, max_iterations, do_e
     """eigenvector_centrality.pyx:57-136.  Returns (vertices, values)."""
     return _centrality("cugraph_eigenvector_centrality", resource_handle, graph, float(epsilon),
                        int(max_iterations), int(bool(do_expensive_check)))
+
+
+def _betweenness_sources(resource_handle, graph, k, random_state):
+    """The source list of a betweenness call as a view of the graph's vertex type, or None for every
+    vertex.  An int draws ``random.Random(random_state).sample(range(n), k)``: positions in the
+    order of the result's ``vertices`` (the reference samples indices, not identifiers,
+    betweenness_centrality.py:298-309)."""
+    if k is None:
+        return None
+    import random
+    import numpy as np
+    if isinstance(k, (int, np.integer)) and not isinstance(k, bool):
+        n = graph.number_of_vertices()
+        if k < 0 or k > n:
+            raise ValueError(f"'k' must be in [0, {n}], got: {k}")
+        picks = random.Random(random_state).sample(range(n), int(k))
+        # the ids at those positions: a call without sources returns the number map and does no work
+        empty = DeviceView(to_device_tensor(np.empty(0, np.int64)).to(graph._vertex_dtype))
+        vertices, _ = _centrality("cugraph_betweenness_centrality", resource_handle, graph, empty.ptr, 0, 0, 0)
+        ids = vertices[to_device_tensor(np.asarray(picks, np.int64))]
+        return DeviceView(ids.contiguous())
+    if isinstance(k, (list, tuple)):  # plain Python ids have no type of their own: the graph's
+        return DeviceView(to_device_tensor(np.asarray(k, np.int64)), graph._vertex_dtype)
+    return DeviceView(k)  # an array keeps its type; another one than the graph's is refused by the C entry
+
+
+def betweenness_centrality(resource_handle, graph, k, random_state, normalized, include_endpoints,
+                           do_expensive_check):
+    """The C entry cugraph_betweenness_centrality with the signature later pylibcugraph releases give it.
+    ``k``: None (every vertex is a source), an int (that many sources, drawn with
+    ``random.Random(random_state)``) or an array of vertex ids of the graph's vertex type (every entry a
+    source).  Returns (vertices, values); the values are float64."""
+    src = _betweenness_sources(resource_handle, graph, k, random_state)
+    return _centrality("cugraph_betweenness_centrality", resource_handle, graph, vptr(src), int(bool(normalized)),
+                       int(bool(include_endpoints)), int(bool(do_expensive_check)))
+
+
+def edge_betweenness_centrality(resource_handle, graph, k, random_state, normalized, do_expensive_check):
+    """The C entry cugraph_edge_betweenness_centrality; ``k`` as in ``betweenness_centrality``.  Returns
+    (src, dst, values): one entry per stored edge in the order of the graph's out-edge rows (both
+    directions of an edge of a symmetric graph), float64 values."""
+    src = _betweenness_sources(resource_handle, graph, k, random_state)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_edge_betweenness_centrality", resource_handle.ptr, graph.c_graph_ptr, vptr(src),
+              int(bool(normalized)), int(bool(do_expensive_check)), ctypes.byref(res))
+    s, d, x = views_to_tensors_owned(resource_handle.ptr,
+                                     [_lib.lib.cugraph_edge_centrality_result_get_src_vertices(res),
+                                      _lib.lib.cugraph_edge_centrality_result_get_dst_vertices(res),
+                                      _lib.lib.cugraph_edge_centrality_result_get_values(res)],
+                                     res, _lib.lib.cugraph_edge_centrality_result_free)
+    return s, d, x
 
 
 def hits(resource_handle, graph, tol, max_iter, initial_hubs_guess_vertices, initial_hubs_guess_values,

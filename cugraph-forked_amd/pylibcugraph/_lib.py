@@ -98,6 +98,12 @@ _proto("cugraph_centrality_result_get_values", P, P)
 _proto("cugraph_centrality_result_free", None, P)
 _proto("cugraph_katz_centrality", c_int, P, P, P, c_double, c_double, c_double, c_size_t, c_int, PP, PP)
 _proto("cugraph_eigenvector_centrality", c_int, P, P, c_double, c_size_t, c_int, PP, PP)
+_proto("cugraph_betweenness_centrality", c_int, P, P, P, c_int, c_int, c_int, PP, PP)
+_proto("cugraph_edge_betweenness_centrality", c_int, P, P, P, c_int, c_int, PP, PP)
+_proto("cugraph_edge_centrality_result_get_src_vertices", P, P)
+_proto("cugraph_edge_centrality_result_get_dst_vertices", P, P)
+_proto("cugraph_edge_centrality_result_get_values", P, P)
+_proto("cugraph_edge_centrality_result_free", None, P)
 _proto("cugraph_hits", c_int, P, P, c_double, c_size_t, P, P, c_int, c_int, PP, PP)
 _proto("cugraph_hits_result_get_vertices", P, P)
 _proto("cugraph_hits_result_get_hubs", P, P)

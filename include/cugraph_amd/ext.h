@@ -135,7 +135,11 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * random walks: the seed of the draw defined in cugraph_c/sampling_algorithms.h, an integer in [0, 2^53), default
  * 0; the one of these options that changes a result), sample_path (neighbour sampling without replacement: 0 the
  * Floyd sampler of a slot goes to a thread or a wave by the fan-out | 1 always a thread | 2 always a wave; the
- * sample is the same under all three); "defaults" resets them all.  Booleans
+ * sample is the same under all three), bc_batch (betweenness: sources per batch, one per lane of a wave, an
+ * integer in [1, 64], default 64; the state is vertices x batch x 20 bytes and the batch is halved while that
+ * does not fit in free device memory), bc_row_split (betweenness: a row above this many entries is cut into
+ * segments of that many, a wave each; a multiple of 64, at least 64, default 2048; neither option changes a bit
+ * of a vertex score, and bc_row_split none of an edge score); "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,

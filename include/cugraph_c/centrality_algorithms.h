@@ -91,6 +91,61 @@ cugraph_error_code_t cugraph_katz_centrality(const cugraph_resource_handle_t* ha
                                              cugraph_centrality_result_t** result,
                                              cugraph_error_t** error);
 
+/*
+ * Betweenness centrality and edge betweenness centrality.  The 22.10 snapshot of the reference declares
+ * neither in its C API (its Python layer reaches centrality/betweenness_centrality.cu through Cython); the
+ * names and the argument order are the ones later cuGraph releases give these calls, the scores and their
+ * scaling are the 22.10 implementation's (betweenness_centrality.cu:368-452).
+ *
+ * Brandes' algorithm on the unweighted graph (weights are ignored).  vertex_list holds the sources as
+ * external ids of the graph's vertex type, every entry a source (a repeated id counts again); NULL means
+ * every vertex.  With n vertices and k sources (k = n for NULL):
+ *   vertex scores: normalized and n > 2: divided by (n - 1)(n - 2), or n(n - 1) with include_endpoints;
+ *                  not normalized and the graph symmetric: divided by 2;
+ *                  then, if k > 0, n > 2 and (normalized or symmetric): multiplied by n / k;
+ *   edge scores:   normalized and n > 1: divided by n(n - 1); not normalized and symmetric: divided by 2.
+ * Parallel edges count as distinct paths, self-loops contribute nothing.
+ *
+ * The values are always FLOAT64, whatever the graph's weight type: the scores are computed in double and
+ * narrowing them is the caller's choice.  The vertex result is a cugraph_centrality_result_t (vertices: the
+ * number map).  The edge result has one entry per stored edge, in the order of the graph's out-edge rows,
+ * with external ids; a symmetric graph reports both directions of an edge.
+ *
+ * Errors: CUGRAPH_NOT_IMPLEMENTED for a multi-GPU graph; CUGRAPH_INVALID_INPUT for a vertex_list of
+ * another type than the graph's vertices or one that holds an id the graph does not have (checked with or
+ * without do_expensive_check).
+ */
+typedef struct {
+  int32_t align_;
+} cugraph_edge_centrality_result_t;
+
+cugraph_error_code_t cugraph_betweenness_centrality(
+  const cugraph_resource_handle_t* handle,
+  cugraph_graph_t* graph,
+  const cugraph_type_erased_device_array_view_t* vertex_list,
+  bool_t normalized,
+  bool_t include_endpoints,
+  bool_t do_expensive_check,
+  cugraph_centrality_result_t** result,
+  cugraph_error_t** error);
+
+cugraph_error_code_t cugraph_edge_betweenness_centrality(
+  const cugraph_resource_handle_t* handle,
+  cugraph_graph_t* graph,
+  const cugraph_type_erased_device_array_view_t* vertex_list,
+  bool_t normalized,
+  bool_t do_expensive_check,
+  cugraph_edge_centrality_result_t** result,
+  cugraph_error_t** error);
+
+cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_src_vertices(
+  cugraph_edge_centrality_result_t* result);
+cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_dst_vertices(
+  cugraph_edge_centrality_result_t* result);
+cugraph_type_erased_device_array_view_t* cugraph_edge_centrality_result_get_values(
+  cugraph_edge_centrality_result_t* result);
+void cugraph_edge_centrality_result_free(cugraph_edge_centrality_result_t* result);
+
 /* HITS result, reference centrality_algorithms.h:238-290 */
 typedef struct {
   int32_t align_;
