@@ -89,6 +89,9 @@ struct tuning_t {
                                 // V x batch x 20 bytes of state do not fit; betweenness.hip)
   int64_t bc_row_split = 2048;  // betweenness: a row above this many entries is cut into segments of that many, a
                                 // wave each (a multiple of 64, the block of a row's sum: the cut changes no bit)
+  int kt_path          = 0;     // k-truss: 0 a frontier edge (and an edge of the support pass) goes to a thread, a wave
+                                // or the split tier by its row sizes, 1 every one to a thread, 2 every one to a wave
+                                // (k_truss.hip)
 };
 
 struct handle_t {
@@ -332,6 +335,20 @@ struct adjacency_t {
   // left to right; built on the first call
   bool cum_valid = false;
   buffer cum;             // double[E]
+  // k-truss (k_truss.hip): the simple rows (the adjacency's own when it holds no loop and no repeat, else a
+  // cleaned copy), one id per undirected edge at every position of them, and every edge's triangle support;
+  // none of it depends on k.  Built on the first call
+  bool kt_valid = false;
+  bool kt_clean = true;      // no loop, no repeat: kt_off / kt_idx / kt_orig stay empty
+  int64_t kt_edges = 0;      // undirected edges of the simple graph
+  int64_t kt_heavy = 0;      // those whose two rows both have k_truss.hip kKtSplitMin entries or more
+  buffer kt_off;             // edge_t[V + 1]   cleaned copy: offsets,
+  buffer kt_idx;             // vertex_t[...]   entries,
+  buffer kt_orig;            // edge_t[...]     and the stored position each entry came from
+  buffer kt_eid;             // edge_t[entries of the simple rows]: the edge's id
+  buffer kt_esrc;            // vertex_t[kt_edges]: the smaller endpoint u of edge (u, v), u < v
+  buffer kt_epos;            // edge_t[kt_edges]: the position of v in u's simple row
+  buffer kt_sup;             // int32[kt_edges]: |N(u) & N(v)|
   pr_push_t pr;  // PageRank windowed-push schedule (pagerank.hip), built on first use
 };
 
@@ -390,6 +407,13 @@ struct k_core_result_t {  // reference c_api/core_result.hpp
   std::unique_ptr<device_array_t> src;
   std::unique_ptr<device_array_t> dst;
   std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
+};
+
+struct induced_subgraph_result_t {  // k-truss; the layout of later releases' c_api/induced_subgraph_result.hpp
+  std::unique_ptr<device_array_t> src;
+  std::unique_ptr<device_array_t> dst;
+  std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
+  std::unique_ptr<device_array_t> offsets;  // {0, edges}: 8-byte values, typed INT64 (this ABI has no SIZE_T id)
 };
 
 struct vertex_pairs_t {  // reference c_api/graph_helper / vertex_pairs.hpp

@@ -1,6 +1,6 @@
 // libcugraph_c algorithm entry points on the hot path (MI355X build):
 // PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components, triangle
-// counting, core number / k-core and their result objects.
+// counting, core number / k-core, k-truss and their result objects.
 //
 // Argument checks and error behaviour follow cpp/src/c_api/{pagerank.cpp:244-304,
 // bfs.cpp:187-230, sssp.cpp:146-190, louvain.cpp:152-190} and the result getters
@@ -35,6 +35,7 @@ void run_triangle_count(handle_t& h, graph_t& g, array_view_t const* start, bool
 void run_core_number(handle_t& h, graph_t& g, int delta, bool expensive, core_result_t& res);
 void run_k_core(handle_t& h, graph_t& g, size_t k, int delta, core_result_t const* given, bool expensive,
                 k_core_result_t& res);
+void run_k_truss(handle_t& h, graph_t& g, size_t k, induced_subgraph_result_t& res);
 void run_betweenness(handle_t& h, graph_t& g, array_view_t const* vertex_list, bool normalized, bool endpoints,
                      centrality_result_t* vres, edge_centrality_result_t* eres);
 void mg_run_pagerank(handle_t& h, graph_t& g, array_view_t const* pow_v, array_view_t const* pow_s,
@@ -468,6 +469,61 @@ extern "C" cugraph_type_erased_device_array_view_t* cugraph_k_core_result_get_we
 extern "C" void cugraph_k_core_result_free(cugraph_k_core_result_t* result)
 {
   delete reinterpret_cast<k_core_result_t*>(result);
+}
+
+// ============================================================== k-truss
+// (the names of later releases' c_api/k_truss.cpp and c_api/induced_subgraph_result.cpp; k_truss.hip)
+extern "C" cugraph_error_code_t cugraph_k_truss_subgraph(const cugraph_resource_handle_t* handle,
+                                                        cugraph_graph_t* graph,
+                                                        size_t k,
+                                                        bool_t do_expensive_check,
+                                                        cugraph_induced_subgraph_result_t** result,
+                                                        cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  (void)do_expensive_check;  // the build of the edge ids finds a missing reverse edge either way
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED, "multi-GPU k_truss_subgraph is not implemented in this build");
+    CGX_INPUT(g.symmetric, "Invalid input argument: k_truss_subgraph supports only undirected graphs.");
+    auto res = std::make_unique<induced_subgraph_result_t>();
+    run_k_truss(*H(handle), g, k, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_induced_subgraph_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_sources(
+  cugraph_induced_subgraph_result_t* result)
+{
+  return new_view(reinterpret_cast<induced_subgraph_result_t*>(result)->src.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_destinations(
+  cugraph_induced_subgraph_result_t* result)
+{
+  return new_view(reinterpret_cast<induced_subgraph_result_t*>(result)->dst.get());
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_edge_weights(
+  cugraph_induced_subgraph_result_t* result)
+{
+  auto* r = reinterpret_cast<induced_subgraph_result_t*>(result);
+  return r->weights ? new_view(r->weights.get()) : nullptr;
+}
+
+extern "C" cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_subgraph_offsets(
+  cugraph_induced_subgraph_result_t* result)
+{
+  return new_view(reinterpret_cast<induced_subgraph_result_t*>(result)->offsets.get());
+}
+
+extern "C" void cugraph_induced_subgraph_result_free(cugraph_induced_subgraph_result_t* result)
+{
+  delete reinterpret_cast<induced_subgraph_result_t*>(result);
 }
 
 // ============================================================== Louvain

@@ -602,6 +602,10 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
                 "Invalid input argument: bc_row_split must be a multiple of 64, at least 64");
       t.bc_row_split = (int64_t)value;
     }
+    else if (n == "kt_path") {
+      CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: kt_path must be 0, 1 or 2");
+      i32(t.kt_path);
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

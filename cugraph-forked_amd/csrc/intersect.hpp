@@ -6,9 +6,11 @@
 //   * isect_probe: one lane's share of a wave that looks entries [s0, s1) of the shorter
 //     row up in the longer one by binary search;
 //   * isect_wave_count: the whole wave, with the longer row staged in the wave's LDS
-//     slice when it fits and pays.
+//     slice when it fits and pays;
+//   * isect_merge_at, isect_probe_at, isect_wave_at: the same three with `hit(x, i, j)`,
+//     the positions of x's first copies in the two rows (k_truss.hip).
 // The thread-level pieces and sim_seg_len are plain C++ that a host-only program can
-// include (tests/c/intersect_test.cpp); the wave-level ones need the HIP compiler.
+// include (tests/c/intersect_test.cpp, intersect_at_test.cpp); the wave-level ones need the HIP compiler.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -112,6 +114,51 @@ CGX_ISECT_FN count_t isect_probe(V const* S, long long s0, long long s1, V const
   return c;
 }
 
+// The position-reporting forms (k_truss.hip reads an edge id at each of the two positions):
+// `hit(x, i, j)` gets, once per distinct common id x, the positions of the first copy of x in
+// the two rows -- A[i] == B[j] == x for the merge, S[i] == L[j] == x for the probe.
+template <typename V, typename F>
+CGX_ISECT_FN count_t isect_merge_at(V const* A, long long na, V const* B, long long nb, F const& hit)
+{
+  count_t c   = 0;
+  long long i = 0, j = 0;
+  while (i < na && j < nb) {
+    V const x = A[i], y = B[j];
+    if (x < y) ++i;
+    else if (y < x) ++j;
+    else {
+      hit(x, i, j);
+      ++c;
+      do ++i; while (i < na && A[i] == x);
+      do ++j; while (j < nb && B[j] == x);
+    }
+  }
+  return c;
+}
+
+// one lane's share of entries [s0, s1) of S, as isect_probe; the lower bound is x's first copy in L
+template <typename V, typename F>
+CGX_ISECT_FN count_t isect_probe_at(V const* S, long long s0, long long s1, V const* L, long long nl, int lane,
+                                    F const& hit)
+{
+  count_t c = 0;
+  for (long long i = s0 + lane; i < s1; i += 64) {
+    V const x = S[i];
+    if (i > 0 && S[i - 1] == x) continue;
+    long long lo = 0, hi = nl;
+    while (lo < hi) {
+      long long const mid = (lo + hi) >> 1;
+      if (L[mid] < x) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < nl && L[lo] == x) {
+      hit(x, i, lo);
+      ++c;
+    }
+  }
+  return c;
+}
+
 #if defined(__HIPCC__)
 __device__ __forceinline__ void bump(count_t* p, count_t c)
 {
@@ -146,6 +193,26 @@ __device__ __forceinline__ count_t isect_wave_count(V const* S, long long s0, lo
     cw = isect_probe<V>(S, s0, s1, L, nl, lane, hit);
   }
   return (count_t)wave_sum_ll((long long)cw);
+}
+// the same by isect_probe_at: `hit` gets positions in S and in L (staged or not, the position is L's);
+// returns this lane's hits, nothing is summed
+template <typename V, typename F>
+__device__ __forceinline__ count_t isect_wave_at(V const* S, long long s0, long long s1, V const* L, long long nl,
+                                                 V* stage, int stage_div, int lane, F const& hit)
+{
+  count_t c;
+  if (nl <= kIsectStageLen<V> && (s1 - s0) * stage_div >= nl) {
+    __builtin_amdgcn_wave_barrier();
+    for (long long j = lane; j < nl; j += 64) stage[j] = L[j];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    c = isect_probe_at<V>(S, s0, s1, (V const*)stage, nl, lane, hit);
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    c = isect_probe_at<V>(S, s0, s1, L, nl, lane, hit);
+  }
+  return c;
 }
 // (The ballot loop that hands a wave its heavy items one after the other stays in the kernels:
 // as a helper taking a lambda it cost no register but rescheduled the loop head, and similarity's

@@ -432,6 +432,55 @@ def k_core(G, k=None, core_number=None):
     return out
 
 
+def ktruss_subgraph(G, k, use_weights=True):
+    """community/ktruss_subgraph.py:91-188.  The k-truss of G as a Graph of G's type: the maximal
+    subgraph in which every edge lies in at least ``k - 2`` triangles of the subgraph (the
+    reference's convention and ``networkx.k_truss``'s), so ``k <= 2`` keeps every edge.  Computed on
+    the underlying simple graph.  G's weights are carried unless ``use_weights`` is False.  A k that
+    leaves no edge gives a graph without edges.  Undirected graphs only; unlike the reference there
+    is no CUDA-version check."""
+    import pandas as pd
+    if G.is_directed():
+        raise ValueError("input graph must be undirected")
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 0:
+        raise ValueError(f"'k' must be a non-negative integer, got: {k}")
+    out = type(G)()
+    p = _plc()
+    src, dst, w, _ = p.k_truss_subgraph(p.ResourceHandle(), G._plc_graph, int(k), False)
+    src, dst = src.cpu().numpy(), dst.cpu().numpy()
+    w = None if (w is None or not use_weights) else w.cpu().numpy()
+    if len(src):
+        cols = {"src": src, "dst": dst}
+        if w is not None:
+            cols["weights"] = w
+        out.from_pandas_edgelist(pd.DataFrame(cols), "src", "dst", "weights" if w is not None else None,
+                                 renumber=G._renumber, store_transposed=G.store_transposed)
+    return out
+
+
+def k_truss(G, k):
+    """community/ktruss_subgraph.py:30-88, the NetworkX-facing twin of ``ktruss_subgraph``: a
+    NetworkX graph gives ``networkx.k_truss(G, k)`` as an ``nx.Graph`` with the original labels (and
+    weights where G has them), a cugraph Graph gives ``ktruss_subgraph(G, k)``."""
+    if G.is_directed():
+        raise ValueError("input graph must be undirected")
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 0:
+        raise ValueError(f"'k' must be a non-negative integer, got: {k}")
+    if not _is_nx(G):
+        return ktruss_subgraph(G, k)
+    import networkx as nx
+    nxv = _NxView(G)
+    p = _plc()
+    src, dst, w, _ = p.k_truss_subgraph(p.ResourceHandle(), nxv.G._plc_graph, int(k), False)
+    labels_s, labels_d = nxv.label(src.cpu().numpy()), nxv.label(dst.cpu().numpy())
+    res = nx.Graph()
+    if w is None:
+        res.add_edges_from(zip(labels_s, labels_d))
+    else:
+        res.add_weighted_edges_from(zip(labels_s, labels_d, w.cpu().numpy().tolist()))
+    return res
+
+
 def _similarity(G, vertex_pair, measure):
     """link_prediction/jaccard.py:21-134 and its siblings, for one of 'jaccard', 'sorensen',
     'overlap'."""

@@ -8,7 +8,8 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 ``louvain`` (louvain.pyx:58-149), ``weakly_connected_components``
 (weakly_connected_components.pyx, components/_connectivity.pyx:132-220), ``triangle_count``
 (triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140), ``k_core`` (the C
-entry of core_algorithms.h), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
+entry of core_algorithms.h), ``k_truss_subgraph`` (the signature of later pylibcugraph releases;
+22.10 reaches its legacy k-truss from cugraph only), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
 ``overlap_coefficients`` (jaccard_coefficients.pyx:58-150 and its siblings) and
 ``get_two_hop_neighbors`` (the C entry of graph_functions.h), ``uniform_neighbor_sample``
 (uniform_neighbor_sample.pyx), ``uniform_random_walks`` / ``biased_random_walks`` (uniform_random_walks.pyx) and
@@ -32,7 +33,8 @@ __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", 
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "betweenness_centrality",
            "edge_betweenness_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
-           "core_number", "k_core", "jaccard_coefficients", "sorensen_coefficients", "overlap_coefficients",
+           "core_number", "k_core", "k_truss_subgraph", "jaccard_coefficients", "sorensen_coefficients",
+           "overlap_coefficients",
            "get_two_hop_neighbors", "uniform_neighbor_sample", "uniform_random_walks", "biased_random_walks",
            "node2vec", "version"]
 
@@ -605,6 +607,29 @@ def k_core(resource_handle, graph, k, degree_type, core_result, do_expensive_che
         ptrs.append(w)
     out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_k_core_result_free)
     return out[0], out[1], (out[2] if w else None)
+
+
+def k_truss_subgraph(resource_handle, graph, k, do_expensive_check):
+    """C entry cugraph_k_truss_subgraph (community_algorithms.h; the name and return tuple of later
+    pylibcugraph releases).  Returns (sources, destinations, edge_weights or None, subgraph_offsets):
+    the stored edges, both directions of each, of the k-truss -- the maximal subgraph in which every
+    edge lies in at least ``k - 2`` triangles of the subgraph, ``networkx.k_truss``'s convention --
+    in the order of the graph's rows.  ``k <= 2`` gives every edge of the underlying simple graph;
+    self-loops and repeated entries neither count nor come back.  ``subgraph_offsets`` is the int64
+    pair [0, number of edges].  The graph must be symmetric (ValueError otherwise)."""
+    if isinstance(k, bool) or int(k) != k or int(k) < 0:
+        raise ValueError(f"'k' must be a non-negative integer, got: {k}")
+    h = resource_handle.ptr
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_k_truss_subgraph", h, graph.c_graph_ptr, int(k), int(bool(do_expensive_check)),
+              ctypes.byref(res))
+    ptrs = [_lib.lib.cugraph_induced_subgraph_get_sources(res), _lib.lib.cugraph_induced_subgraph_get_destinations(res),
+            _lib.lib.cugraph_induced_subgraph_get_subgraph_offsets(res)]
+    w = _lib.lib.cugraph_induced_subgraph_get_edge_weights(res)
+    if w:
+        ptrs.append(w)
+    out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_induced_subgraph_result_free)
+    return out[0], out[1], (out[3] if w else None), out[2]
 
 
 def _similarity(api, resource_handle, graph, first, second, use_weight, do_expensive_check):

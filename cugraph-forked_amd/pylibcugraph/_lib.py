@@ -140,6 +140,12 @@ _proto("cugraph_k_core_result_get_src_vertices", P, P)
 _proto("cugraph_k_core_result_get_dst_vertices", P, P)
 _proto("cugraph_k_core_result_get_weights", P, P)
 _proto("cugraph_k_core_result_free", None, P)
+_proto("cugraph_k_truss_subgraph", c_int, P, P, c_size_t, c_int, PP, PP)
+_proto("cugraph_induced_subgraph_get_sources", P, P)
+_proto("cugraph_induced_subgraph_get_destinations", P, P)
+_proto("cugraph_induced_subgraph_get_edge_weights", P, P)
+_proto("cugraph_induced_subgraph_get_subgraph_offsets", P, P)
+_proto("cugraph_induced_subgraph_result_free", None, P)
 _proto("cugraph_create_vertex_pairs", c_int, P, P, P, P, PP, PP)
 _proto("cugraph_vertex_pairs_get_first", P, P)
 _proto("cugraph_vertex_pairs_get_second", P, P)

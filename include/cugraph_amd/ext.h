@@ -139,7 +139,9 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * integer in [1, 64], default 64; the state is vertices x batch x 20 bytes and the batch is halved while that
  * does not fit in free device memory), bc_row_split (betweenness: a row above this many entries is cut into
  * segments of that many, a wave each; a multiple of 64, at least 64, default 2048; neither option changes a bit
- * of a vertex score, and bc_row_split none of an edge score); "defaults" resets them all.  Booleans
+ * of a vertex score, and bc_row_split none of an edge score), kt_path (k-truss: 0 a frontier edge of the peel and
+ * an edge of the support pass go to a thread, a wave or the split tier by their row sizes | 1 always a thread |
+ * 2 always a wave; the result, its order included, is the same under all three); "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,

@@ -5,6 +5,7 @@
 #pragma once
 #include <cugraph_c/error.h>
 #include <cugraph_c/graph.h>
+#include <cugraph_c/graph_functions.h>
 #include <cugraph_c/resource_handle.h>
 
 #ifdef __cplusplus
@@ -70,6 +71,32 @@ double cugraph_heirarchical_clustering_result_get_modularity(
 
 /* reference community_algorithms.h:136 */
 void cugraph_heirarchical_clustering_result_free(cugraph_heirarchical_clustering_result_t* result);
+
+/*
+ * k-truss subgraph (the name and signature of later cuGraph releases; the 22.10 reference reaches
+ * community/legacy/ktruss.cu from Python only).  Kernels: csrc/k_truss.hip.
+ *
+ * The k-truss is the maximal subgraph in which every edge lies in at least k - 2 triangles of the
+ * subgraph (the reference's convention, and networkx.k_truss's); k <= 2 returns every edge.  The
+ * algorithm runs on the underlying simple graph: self-loops and repeated row entries neither form nor
+ * count triangles and are not emitted; a repeated entry is represented by its first stored copy, weight
+ * included.
+ *
+ * The result (graph_functions.h) holds the surviving stored edges, both directions of each, in external
+ * ids and in the order of the graph's out-edge rows: the same from call to call and under every value of
+ * the handle option kt_path.  Weights are carried bit for bit when the graph has them, otherwise the
+ * weights view is NULL.  The result is a pure function of the graph and k.
+ *
+ * CUGRAPH_INVALID_INPUT: graph NULL, or a graph that is not symmetric.  CUGRAPH_NOT_IMPLEMENTED: a
+ * multi-GPU graph.  *result is NULL on error.  do_expensive_check adds nothing: a missing reverse edge
+ * is found while the edge ids are built and is CUGRAPH_INVALID_INPUT either way.
+ */
+cugraph_error_code_t cugraph_k_truss_subgraph(const cugraph_resource_handle_t* handle,
+                                              cugraph_graph_t* graph,
+                                              size_t k,
+                                              bool_t do_expensive_check,
+                                              cugraph_induced_subgraph_result_t** result,
+                                              cugraph_error_t** error);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,33 @@ cugraph_error_code_t cugraph_two_hop_neighbors(const cugraph_resource_handle_t* 
                                                cugraph_vertex_pairs_t** result,
                                                cugraph_error_t** error);
 
+/*
+ * An extracted subgraph as an edge list (the type and getters of later cuGraph releases' graph_functions.h;
+ * the 22.10 reference has none).  cugraph_k_truss_subgraph (community_algorithms.h) returns one.
+ */
+typedef struct { int32_t align_; } cugraph_induced_subgraph_result_t;
+
+/* external ids, vertex type */
+cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_sources(
+  cugraph_induced_subgraph_result_t* induced_subgraph);
+
+/* external ids, vertex type */
+cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_destinations(
+  cugraph_induced_subgraph_result_t* induced_subgraph);
+
+/* weight type, edge i's weight; NULL when the graph has no weights */
+cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_edge_weights(
+  cugraph_induced_subgraph_result_t* induced_subgraph);
+
+/*
+ * Two size_t values {0, number of edges}: the one subgraph's range in the three arrays.  data_type_id_t
+ * of this ABI has no SIZE_T, so the view's type id is INT64 (the same 8 bytes).
+ */
+cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_subgraph_offsets(
+  cugraph_induced_subgraph_result_t* induced_subgraph);
+
+void cugraph_induced_subgraph_result_free(cugraph_induced_subgraph_result_t* induced_subgraph);
+
 #ifdef __cplusplus
 }
 #endif
