@@ -48,6 +48,8 @@ struct tuning_t {
                                 // 64-entry rows of one (window, source) stored as slots + one source; -1 by
                                 // window size (push_runs_on), 1 on, 0 off
   int64_t pr_run_min   = -1;    // shortest run that gives run rows (-1: kRunMin; at least 64)
+  bool pr_dense        = true;  // dense flags on the packed schedule's wave segments (pagerank.hip kSegDense):
+                                // a flagged segment is decoded four rows per scan; 0 sets no flag
   int pr_share_div     = 0;     // items per push block on average (0: kShareDiv); windows above 1.5x are shared
   bool pr_fast_build   = true;  // symmetric unweighted schedules through one-word keys (else the general build)
   int mg_chunks        = 0;     // MG overlap chunks (0: one chunk, no overlap)
@@ -108,6 +110,8 @@ struct handle_t {
   int64_t last_pr_permuted   = 0;  // and the vertices its x~ layout map moves (0: no map)
   int64_t last_pr_run_rows    = 0;  // its run rows (64 entries of one source each, padding rows not counted)
   int64_t last_pr_run_entries = 0;  // and the entries they hold
+  int64_t last_pr_dense_segs  = 0;  // its packed stream's wave segments flagged dense,
+  int64_t last_pr_packed_segs = 0;  // of this many (run units' segments not counted)
   size_t last_bfs_levels    = 0;
   size_t last_bfs_bottom_up  = 0;
   size_t last_louvain_levels = 0;
@@ -288,6 +292,8 @@ struct pr_push_t {
   // packed stream; their slots follow it in ent16, in units of their own (push_unit::base < 0)
   buffer run_src;          // uint32[rows + a unit's]: the source of every row, kRunPad on padding rows
   int64_t run_rows = 0, run_entries = 0;
+  // wave segments of the packed stream, and those of them flagged dense (pagerank.hip kSegDense)
+  int64_t packed_segs = 0, dense_segs = 0;
   // the last call's iteration count (plain calls: no guess, no personalization) with
   // its alpha and epsilon: the first chunk of the next such call (pagerank.hip)
   int last_iters = 0;

@@ -548,6 +548,7 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value == -1 || value >= 64, "Invalid input argument: pr_run_min must be -1 or at least 64");
       t.pr_run_min = (int64_t)value;
     }
+    else if (n == "pr_dense") b(t.pr_dense);
     else if (n == "pr_fast_build") b(t.pr_fast_build);
     else if (n == "pr_share_div") i32(t.pr_share_div);
     else if (n == "mg_chunks") i32(t.mg_chunks);
@@ -648,6 +649,12 @@ extern "C" void cugraph_amd_last_pagerank_runs(const cugraph_resource_handle_t* 
 {
   *run_rows    = H(handle)->last_pr_run_rows;
   *run_entries = H(handle)->last_pr_run_entries;
+}
+extern "C" void cugraph_amd_last_pagerank_dense(const cugraph_resource_handle_t* handle, int64_t* dense_segments,
+                                                int64_t* packed_segments)
+{
+  *dense_segments  = H(handle)->last_pr_dense_segs;
+  *packed_segments = H(handle)->last_pr_packed_segs;
 }
 extern "C" size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle)
 {

@@ -1081,6 +1081,12 @@ __host__ __device__ __forceinline__ int64_t seg_store_index(int64_t p)
   return (p & ~(int64_t)(kSegEntries - 1)) | ((e & 63) << 3) | (e >> 6);
 }
 constexpr int kSegsPerUnit = kPushUnit / kSegEntries;
+// Bit 31 of a seg_base word (sources are below 2^31, assemble_packed): the segment is dense -- 512
+// consecutive real entries of one window, no jump and no padding, and every 64-entry row's
+// sources rise by at most 255 from the source running before the row (k_seg_bases).  Every reader
+// masks it off; a kernel with the dense path (push_body16 kDense) decodes such a segment four rows
+// per scan.
+constexpr uint32_t kSegDense = 0x80000000u;
 
 // inclusive prefix sum over the 64 lanes of a wave (DPP row shifts + row broadcasts)
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
@@ -1144,6 +1150,8 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
   // (at 4K windows with encoded x~ words only: the plain-float kernel spilled 12 B with it)
   constexpr bool kRuns = WB != 13 && (WB >= 14 || ENC) && !BANDS && sizeof(V) == 4 && std::is_same<R, float>::value;
   constexpr bool kAcc32 = WB == 15;
+  // dense segments (kSegDense, k_seg_bases): the 16K-window hub kernels of 32-bit ids and fp32 ranks
+  constexpr bool kDense = WB == 14 && HUB && !BANDS && sizeof(V) == 4 && std::is_same<R, float>::value;
   using acc_t           = typename std::conditional<kAcc32, uint32_t, unsigned long long>::type;
   __shared__ acc_t acc[kWin];
   constexpr int kHub = HUB ? kHubBytes / (int)sizeof(xw_t) : 1;
@@ -1193,26 +1201,55 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
     // to whole segments), <= 0 for the waves past the end of a window's last unit
     auto seg_n = [&](int64_t u) { return (int)(units[u].k1 - units[u].k0) - wave * kSegEntries; };
     auto entry = [&](u32x4_t const& w, int j) { return (w[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu; };
-    // decode a segment's sources (DPP scan of the deltas + the running base) and
-    // issue its 8 gathers; jumps and padding read a valid source and add nothing to LDS
-    // (an exec-masked add instead of adding 0: RMAT-24 0.577-0.595 vs 0.596-0.599
-    // ms/iteration, same box).  Masking their gathers too was slower (RMAT-24 0.640,
-    // RMAT-26 3.09 vs 3.00 ms): the mask costs registers and exec switches in the loop
-    auto gather = [&](u32x4_t const& w, uint32_t base, xw_t (&xv)[kRows]) {
-      uint32_t sc[kRows];
+    // a segment's deltas (a jump entry's payload), scanned row by row
+    auto scan_rows = [&](u32x4_t const& w, uint32_t (&sc)[kRows]) {
 #pragma unroll
       for (int j = 0; j < kRows; ++j) {
         uint32_t const e = entry(w, j);
         sc[j]            = (e >> WB) == kJump ? (e & kLow) : (e >> WB);
       }
       wave_incl_scan_rows<kRows>(sc);
-      uint32_t run = base;
+    };
+    // Sources of a dense segment (kSegDense): 512 real entries, no jump, every row's deltas sum to
+    // <= 255.  Four rows' deltas go into the four bytes of one word (no carry crosses a byte), so
+    // two chains of six DPP adds scan the segment instead of eight, with no jump compare or select
+    // in front; the rows' totals are the bytes of lane 63, taken apart on the scalar unit.  Word h
+    // holds rows 4h, 4h + 2, 4h + 1, 4h + 3 in bytes 0 .. 3.  run: the base in, the last source out.
+    auto dense_sources = [&](u32x4_t const& w, uint32_t& run, uint32_t (&src)[kRows]) {
+      constexpr uint32_t kDelta2 = ((1u << (16 - WB)) - 1) * 0x00010001u;
+      uint32_t c[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) c[h] = ((w[2 * h] >> WB) & kDelta2) | (((w[2 * h + 1] >> WB) & kDelta2) << 8);
+      wave_incl_scan_rows<2>(c);
+      uint32_t const t[2] = {(uint32_t)__builtin_amdgcn_readlane((int)c[0], 63),
+                             (uint32_t)__builtin_amdgcn_readlane((int)c[1], 63)};
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) {
+        int const sh = 8 * (((j & 1) << 1) | ((j >> 1) & 1));
+        src[j]       = run + ((c[j >> 2] >> sh) & 0xFFu);
+        run += (t[j >> 2] >> sh) & 0xFFu;
+      }
+    };
+    // decode a segment's sources (DPP scan of the deltas + the running base) and
+    // issue its 8 gathers; jumps and padding read a valid source and add nothing to LDS
+    // (an exec-masked add instead of adding 0: RMAT-24 0.577-0.595 vs 0.596-0.599
+    // ms/iteration, same box).  Masking their gathers too was slower (RMAT-24 0.640,
+    // RMAT-26 3.09 vs 3.00 ms): the mask costs registers and exec switches in the loop.
+    // base: the seg_base word, wave-uniform; its kSegDense bit picks the dense decode (kDense)
+    auto gather = [&](u32x4_t const& w, uint32_t base, xw_t (&xv)[kRows]) {
+      uint32_t run = base & ~kSegDense;
+      uint32_t sc[kRows];
       if constexpr (HUB) {
         uint32_t src[kRows];
+        if (kDense && (base & kSegDense)) {
+          dense_sources(w, run, src);
+        } else {
+          scan_rows(w, sc);
 #pragma unroll
-        for (int j = 0; j < kRows; ++j) {
-          src[j] = run + sc[j];
-          run += (uint32_t)__builtin_amdgcn_readlane((int)sc[j], 63);
+          for (int j = 0; j < kRows; ++j) {
+            src[j] = run + sc[j];
+            run += (uint32_t)__builtin_amdgcn_readlane((int)sc[j], 63);
+          }
         }
         if (run < nh) {  // wave-uniform: the segment's last source (lane 63 of row 7) is a hub
 #pragma unroll
@@ -1223,6 +1260,7 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
         }
         return;
       }
+      scan_rows(w, sc);
 #pragma unroll
       for (int j = 0; j < kRows; ++j) {
         uint32_t const src = run + sc[j];
@@ -1230,7 +1268,21 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
         xv[j] = x[src];
       }
     };
-    auto sum = [&](u32x4_t const& w, xw_t const (&xv)[kRows]) {
+    // base: the segment's seg_base word again; a dense segment has an edge in every entry, so no
+    // jump test and no exec mask around the add
+    auto sum = [&](u32x4_t const& w, xw_t const (&xv)[kRows], [[maybe_unused]] uint32_t base) {
+      if constexpr (kDense) {
+        if (base & kSegDense) {  // wave-uniform
+#pragma unroll
+          for (int j = 0; j < kRows; ++j) {
+            unsigned long long fix;
+            if constexpr (ENC) fix = dec_fixed(xv[j]);
+            else fix = fixed_of(xv[j]);
+            atomicAdd(&acc[entry(w, j) & kLow], fix);
+          }
+          return;
+        }
+      }
       if constexpr (kAcc32) {
         // A term's low word goes into the 32-bit LDS sum; the old value the add returns
         // says whether it carried out, and a carry (or a term of 2^32 or more: x~ above
@@ -1352,7 +1404,8 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
       u32x4_t wA  = nt_load(seg_ptr(um));  // padded: the stream has a unit past its end
       u32x4_t wB  = nt_load(seg_ptr(u1));
       xw_t xA[kRows];
-      if (nA > 0) gather(wA, __builtin_amdgcn_readfirstlane(sa.seg_base[um * kSegsPerUnit + wave]), xA);
+      uint32_t bA = __builtin_amdgcn_readfirstlane(sa.seg_base[um * kSegsPerUnit + wave]);
+      if (nA > 0) gather(wA, bA, xA);
       for (int64_t un = um; un < ub; ++un) {
         bool const actB = un + 1 < ub && nB > 0;  // wave-uniform
         xw_t xB[kRows];
@@ -1362,8 +1415,9 @@ __device__ __forceinline__ void push_body16(push_args<V, E, R> const& sa)
         uint32_t const b2 = sa.seg_base[u2 * kSegsPerUnit + wave];
         u32x4_t const e2  = nt_load(seg_ptr(u2));
         __builtin_amdgcn_sched_barrier(0);  // keep the next gathers and the prefetch ahead of the sums
-        if (nA > 0) sum(wA, xA);
+        if (nA > 0) sum(wA, xA, bA);
         wA = wB;
+        bA = bB;
 #pragma unroll
         for (int j = 0; j < kRows; ++j) xA[j] = xB[j];
         nA = actB ? nB : 0;
@@ -1809,18 +1863,26 @@ __global__ void k_units_direct(int64_t const* nws, int64_t nwin, uint32_t const*
   }
 }
 
-// running source before the first entry of every (unit, wave segment)
+// running source before the first entry of every (unit, wave segment), and its dense flag
+// (kSegDense; mark_dense off: no flags).  A segment that starts at real entry k with no jump in
+// front of it is 512 consecutive real entries of one window iff entry k + 511 exists, lies in the
+// same window and has the same jump count before it; the rows' source ranges are then seven more
+// key reads.  counts[0] / counts[1]: the packed segments (run units' and the ones past a unit's
+// end not counted) and the dense ones among them.
 template <typename KC, typename CM>
 __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t const* keys, int64_t ne,
                             int64_t const* ws, CM const* cm, unsigned long long const* pb,
-                            uint32_t dmax, uint32_t pmax, uint32_t* seg_base, KC kc)
+                            uint32_t dmax, uint32_t pmax, uint32_t* seg_base, KC kc, bool mark_dense,
+                            unsigned long long* counts)
 {
-  int64_t const n = nunits * kSegsPerUnit;
+  int64_t const n    = nunits * kSegsPerUnit;
+  uint32_t n_packed = 0, n_dense = 0;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     push_unit const u = units[i / kSegsPerUnit];
     int64_t const p   = u.k0 + (i % kSegsPerUnit) * kSegEntries;
     uint32_t base     = 0;
     if (p < u.k1 && u.base >= 0) {  // a segment never starts in a window's padding; run units have no bases
+      ++n_packed;
       int64_t lo = 0, hi = ne - 1;  // first real entry at a packed position >= p
       while (lo < hi) {
         int64_t mid = (lo + hi) >> 1;
@@ -1835,8 +1897,31 @@ __global__ void k_seg_bases(push_unit const* units, int64_t nunits, uint64_t con
       uint32_t const src  = kc.src(keys[k]);
       uint32_t const D    = src - prev;
       base = j < (int64_t)m ? prev + pmax * (uint32_t)j : src - (m ? 0u : (D <= dmax ? D : 0u));
+      int64_t const kl = k + kSegEntries - 1;
+      if (mark_dense && m == 0 && kl < ne && kc.win(keys[kl]) == w && cm[kl] == cm[k]) {
+        bool dense      = true;
+        uint32_t before = base;
+        for (int r = 0; r < kSegEntries / 64; ++r) {
+          uint32_t const last = kc.src(keys[k + r * 64 + 63]);
+          dense               = dense && last - before <= 255u;
+          before              = last;
+        }
+        if (dense) {
+          base |= kSegDense;
+          ++n_dense;
+        }
+      }
     }
     seg_base[i] = base;
+  }
+  // (every lane is back here: the loop's exits are behind it)
+  for (int off = 32; off > 0; off >>= 1) {
+    n_packed += (uint32_t)__shfl_down((int)n_packed, off);
+    n_dense += (uint32_t)__shfl_down((int)n_dense, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (n_packed) atomicAdd(counts, (unsigned long long)n_packed);
+    if (n_dense) atomicAdd(counts + 1, (unsigned long long)n_dense);
   }
 }
 
@@ -2228,6 +2313,7 @@ inline void reset_push(hipStream_t s, pr_push_t& pp, int wb, int64_t nwin, int64
   pp.stream_len = 0;
   pp.run_src.release();
   pp.run_rows = pp.run_entries = 0;
+  pp.packed_segs = pp.dense_segs = 0;
 }
 
 template <typename KC>
@@ -2244,12 +2330,14 @@ void window_starts(hipStream_t s, uint64_t const* keys, int64_t ne, int64_t nwin
 // counts and their prefix (CM: 32 bits while the entries are below 2^31), the windows padded
 // to whole segments, the stream, the run stream behind it, units, segment bases, items.
 // false, with pp untouched: the stream would take more than 1.5 x the entries (run rows
-// included) or 2^32 positions.
+// included) or 2^32 positions, or the nsrc sources do not leave bit 31 of a segment base free
+// (kSegDense).
 template <typename KC, typename CM>
 bool assemble_packed(hipStream_t s, uint64_t const* keys, int64_t ne, uint64_t const* rk_first, int64_t nrk, KC kc,
                      int64_t const* ws, int wb, int64_t nwin, int64_t nwin_real, bool bands, pr_push_t& pp,
-                     tuning_t const& tu)
+                     tuning_t const& tu, int64_t nsrc)
 {
+  if (nsrc > (int64_t(1) << 31)) return false;
   uint32_t const dmax = (1u << (16 - wb)) - 2;  // coded deltas 0 .. dmax; dmax + 1 marks a jump
   uint32_t const pmax = (1u << wb) - 1;         // jump payloads 1 .. pmax
   int64_t const ne_all = ne + nrk;
@@ -2354,15 +2442,20 @@ bool assemble_packed(hipStream_t s, uint64_t const* keys, int64_t ne, uint64_t c
     CGX_LAUNCH_CHECK();
   }
   pp.seg_base.resize(std::max<int64_t>(nunits * kSegsPerUnit, 1) * sizeof(uint32_t), s);
+  dbuf<unsigned long long> seg_counts(2, s);
+  fill<unsigned long long>(seg_counts.data(), 2, 0ull, s);
   if (nunits)
     hipLaunchKernelGGL((k_seg_bases<KC, CM>), dim3(grid_for(nunits * kSegsPerUnit, kBlock, 16384)), dim3(kBlock), 0,
-                       s, units, nunits, keys, ne, ws, cm, pb.data(), dmax, pmax, pp.seg_base.data<uint32_t>(), kc);
+                       s, units, nunits, keys, ne, ws, cm, pb.data(), dmax, pmax, pp.seg_base.data<uint32_t>(), kc,
+                       tu.pr_dense, seg_counts.data());
   CGX_LAUNCH_CHECK();
   pp.ent.release();
   pp.ew.release();
   build_items(s, pp, units, nunits, wb >= 13, tu);
   pp.nunits = nunits;
-  HIP_CHECK(hipStreamSynchronize(s));
+  auto const h_counts = to_host(seg_counts.data(), 2, s);  // (synchronises the stream)
+  pp.packed_segs      = (int64_t)h_counts[0];
+  pp.dense_segs       = (int64_t)h_counts[1];
   return true;
 }
 
@@ -2417,7 +2510,7 @@ void build_push_from_coo(hipStream_t s, uint32_t const* rows, C const* cols, R c
     auto const assemble = ne < (int64_t(1) << 31) ? assemble_packed<key_w32, uint32_t>
                                                   : assemble_packed<key_w32, unsigned long long>;
     if (assemble(s, keys_out.data(), ne, nullptr, 0, key_w32{rows, vals_out.data(), (1u << wb) - 1}, ws.data(), wb, nwin,
-                 nwin_real, band_cut > 0, pp, tu))
+                 nwin_real, band_cut > 0, pp, tu, n_cols))
       return;
   }
   if (band_cut > 0 || wb == 15) {  // bands and 32K windows need the packed format: the schedule without them
@@ -2663,7 +2756,8 @@ bool build_push_packed_sym(hipStream_t s, E const* off, uint32_t const* idx, int
   window_starts(s, kbuf.data(), ne, nwin, kc, ws.data());
   auto const assemble = ne_all < (int64_t(1) << 31) ? assemble_packed<key_p, uint32_t>
                                                     : assemble_packed<key_p, unsigned long long>;
-  if (!assemble(s, kbuf.data(), ne, rk_first, nrk, kc, ws.data(), wb, nwin, nwin_real, band_cut > 0, pp, tu)) return false;
+  if (!assemble(s, kbuf.data(), ne, rk_first, nrk, kc, ws.data(), wb, nwin, nwin_real, band_cut > 0, pp, tu, nv))
+    return false;
   pp.built    = true;
   pp.ok       = true;
   pp.pos      = std::move(pos);
@@ -2944,6 +3038,8 @@ void pagerank_impl(handle_t& h, graph_t& g, array_view_t const* pow_v, array_vie
   h.last_pr_permuted = push && adj.pr.perm_cut ? nv - adj.pr.perm_cut : 0;
   h.last_pr_run_rows    = push ? adj.pr.run_rows : 0;
   h.last_pr_run_entries = push ? adj.pr.run_entries : 0;
+  h.last_pr_dense_segs  = push ? adj.pr.dense_segs : 0;
+  h.last_pr_packed_segs = push ? adj.pr.packed_segs : 0;
   hipLaunchKernelGGL((k_pr_init<V, E, R>), dim3(nblk_init), dim3(kBlock), 0, s, a);
   CGX_LAUNCH_CHECK();
 

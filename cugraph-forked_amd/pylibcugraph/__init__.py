@@ -130,6 +130,14 @@ class ResourceHandle:
         _lib.lib.cugraph_amd_last_pagerank_runs(self.c_resource_handle_ptr, ctypes.byref(n), ctypes.byref(m))
         return n.value, m.value
 
+    def last_pagerank_dense(self):
+        """Dense wave segments of the last single-GPU PageRank call's push schedule:
+        (512-entry segments of the packed stream flagged dense, all its segments);
+        (0, 0) without a packed stream."""
+        n, m = ctypes.c_int64(), ctypes.c_int64()
+        _lib.lib.cugraph_amd_last_pagerank_dense(self.c_resource_handle_ptr, ctypes.byref(n), ctypes.byref(m))
+        return n.value, m.value
+
     def measure_copy_bandwidth(self, nbytes=4 << 30, reps=10):
         """HBM ceiling: 16-B-per-lane copy kernel on this handle's stream, GB/s (read + write)."""
         r = _lib.lib.cugraph_amd_measure_copy_bandwidth(self.c_resource_handle_ptr, int(nbytes), int(reps))

@@ -209,6 +209,7 @@ _proto("cugraph_amd_last_louvain_sweep_bytes", c_double, P)
 _proto("cugraph_amd_last_louvain_partition", None, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64))
 _proto("cugraph_amd_last_pagerank_schedule", None, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64))
 _proto("cugraph_amd_last_pagerank_runs", None, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64))
+_proto("cugraph_amd_last_pagerank_dense", None, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64))
 _proto("cugraph_amd_trim_device_cache", c_size_t)
 _proto("cugraph_amd_allocator_stats", None, ctypes.POINTER(c_double))
 _proto("cugraph_amd_version", ctypes.c_char_p)

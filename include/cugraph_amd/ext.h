@@ -120,6 +120,10 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * and 32-bit ids only, and never at 8K windows (pr_win_bits 13) nor at 4K windows with pr_enc 0: those
  * kernels have no path for such rows, 1 is then ignored and cugraph_amd_last_pagerank_runs reports 0),
  * pr_run_min (shortest run that gives such rows, at least 64; -1: the default),
+ * pr_dense (dense flags on the 512-entry wave segments of a packed 16-bit schedule -- 512 real entries of one
+ * window, no jump, no padding, every 64-entry row's sources rising by at most 255: 1 | 0, default 1; the
+ * 16K-window kernels of 32-bit ids and fp32 ranks decode a flagged segment four rows per scan, the others
+ * ignore the flag; 0 sets none; the sums are the same integers either way),
  * mg_bfs_alpha, mg_bfs_beta, mg_bfs_pipelined (1 | 0), pr_fast_build, pr_share_div (0 | n),
  * mg_chunks, bfs_alpha, bfs_beta, bfs_probe_vec, bfs_head, bfs_res_grid,
  * bfs_probe_grid, bfs_td_cap, louvain_hash, louvain_big_hash, louvain_big_cap,
@@ -157,6 +161,11 @@ void cugraph_amd_last_pagerank_schedule(const cugraph_resource_handle_t* handle,
  * rows that only pad a window are not counted) and the entries they hold (64 x rows); 0, 0 without them.
  * These entries are not part of cugraph_amd_last_pagerank_schedule's packed stream. */
 void cugraph_amd_last_pagerank_runs(const cugraph_resource_handle_t* handle, int64_t* run_rows, int64_t* run_entries);
+/* PageRank (single GPU): the 512-entry wave segments of the last call's packed 16-bit stream that carry the
+ * dense flag (option pr_dense), and all of its segments (run rows' segments not counted); 0, 0 for the other
+ * entry formats or the pull path. */
+void cugraph_amd_last_pagerank_dense(const cugraph_resource_handle_t* handle, int64_t* dense_segments,
+                                     int64_t* packed_segments);
 /* BFS: edges examined, levels, top-down/bottom-up steps of the last call */
 size_t cugraph_amd_last_bfs_levels(const cugraph_resource_handle_t* handle);
 size_t cugraph_amd_last_bfs_bottom_up_steps(const cugraph_resource_handle_t* handle);

@@ -3,7 +3,7 @@
 usage: pr_ab.py SCALE [NAME=VAL,NAME=VAL ...] ...
 Builds the bench's R-MAT graph for every argument (a comma list of handle
 options, include/cugraph_amd/ext.h cugraph_amd_set_option, e.g. pr_enc=0,pr_hub=0
-or pr_runs=1,pr_run_min=128, or "base") runs 2 warm and 5 timed PageRank calls and prints ms per iteration from
+or pr_runs=1,pr_run_min=128, or pr_dense=0, or "base") runs 2 warm and 5 timed PageRank calls and prints ms per iteration from
 the library's HIP events (h.last_hot_kernel_ms / launches).  Every call
 runs exactly 16 iterations (epsilon 0, max 16: the "failed to converge" error is
 expected and ignored), so ablations that change the ranks keep the same work.
@@ -52,8 +52,10 @@ def main():
             h.set_profiling(False)
             stream, moved = h.last_pagerank_schedule()
             rows, in_rows = h.last_pagerank_runs()
+            dense, packed = h.last_pagerank_dense()
             print(f"RMAT-{scale} {arg}: {ms / max(n, 1):.4f} ms/iteration ({it / 5:.0f} iterations, "
                   f"{E * it / 5 / (ms / 5 * 1e-3) / 1e9:.1f} Gedges/s; {stream} stream entries, "
+                  f"{dense} of {packed} packed segments dense, "
                   f"{rows} run rows holding {in_rows} entries, "
                   f"{moved} vertices moved by the x~ layout)", flush=True)
         finally:
