@@ -94,6 +94,13 @@ struct tuning_t {
   int kt_path          = 0;     // k-truss: 0 a frontier edge (and an edge of the support pass) goes to a thread, a wave
                                 // or the split tier by its row sizes, 1 every one to a thread, 2 every one to a wave
                                 // (k_truss.hip)
+  int sg_path          = 0;     // induced subgraph / ego net extraction: 0 a (subgraph, member) row goes to a thread, a
+                                // wave or the split tier by its length, 1 every row to a thread, 2 every row to a
+                                // wave (subgraph.hip)
+  int64_t sg_split_min = 64;    // extraction: a row of at least this many entries is cut into segments of
+                                // kSgSegLen entries, a wave each (sg_path 0 only; at least 1)
+  int64_t ego_budget   = (int64_t)1 << 26;  // ego nets: candidate keys expanded and sorted per batch of whole source
+                                // slots; a slot whose hop alone exceeds it goes through a V-bit map (subgraph.hip)
 };
 
 struct handle_t {
@@ -415,11 +422,14 @@ struct k_core_result_t {  // reference c_api/core_result.hpp
   std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
 };
 
-struct induced_subgraph_result_t {  // k-truss; the layout of later releases' c_api/induced_subgraph_result.hpp
+// k-truss (one subgraph), induced subgraphs and ego nets (one per vertex set / source); the layout of later
+// releases' c_api/induced_subgraph_result.hpp
+struct induced_subgraph_result_t {
   std::unique_ptr<device_array_t> src;
   std::unique_ptr<device_array_t> dst;
   std::unique_ptr<device_array_t> weights;  // null for an unweighted graph
-  std::unique_ptr<device_array_t> offsets;  // {0, edges}: 8-byte values, typed INT64 (this ABI has no SIZE_T id)
+  std::unique_ptr<device_array_t> offsets;  // subgraphs + 1 entries, subgraph i = edges [offsets[i], offsets[i + 1]);
+                                            // 8-byte values, typed INT64 (this ABI has no SIZE_T id)
 };
 
 struct vertex_pairs_t {  // reference c_api/graph_helper / vertex_pairs.hpp
@@ -531,5 +541,12 @@ void unrenumber_int_to_ext(handle_t& h, graph_t& g, void* ids, size_t n);
 std::unique_ptr<device_array_t> number_map_copy(handle_t& h, graph_t& g);
 // per-vertex out-weight sums in weight_t (cached on the graph)
 void const* out_weight_sums(handle_t& h, graph_t& g);
+
+// ------------------------------------------------------------------ subgraph extraction
+// (subgraph.hip)  offsets: INT64 [subgraphs + 1], vertices / sources: external ids in the graph's vertex type
+void run_induced_subgraph(handle_t& h, graph_t& g, array_view_t const& offsets, array_view_t const& vertices,
+                          induced_subgraph_result_t& res);
+void run_extract_ego(handle_t& h, graph_t& g, array_view_t const& sources, size_t radius,
+                     induced_subgraph_result_t& res);
 
 }  // namespace cgx

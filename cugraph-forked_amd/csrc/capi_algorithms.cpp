@@ -1,6 +1,6 @@
 // libcugraph_c algorithm entry points on the hot path (MI355X build):
 // PageRank, personalised PageRank, BFS, SSSP, Louvain, connected components, triangle
-// counting, core number / k-core, k-truss and their result objects.
+// counting, core number / k-core, k-truss, induced subgraphs / ego nets and their result objects.
 //
 // Argument checks and error behaviour follow cpp/src/c_api/{pagerank.cpp:244-304,
 // bfs.cpp:187-230, sssp.cpp:146-190, louvain.cpp:152-190} and the result getters
@@ -491,6 +491,66 @@ extern "C" cugraph_error_code_t cugraph_k_truss_subgraph(const cugraph_resource_
     CGX_INPUT(g.symmetric, "Invalid input argument: k_truss_subgraph supports only undirected graphs.");
     auto res = std::make_unique<induced_subgraph_result_t>();
     run_k_truss(*H(handle), g, k, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_induced_subgraph_result_t*>(res.release());
+  });
+}
+
+// ============================================================== induced subgraphs and ego nets
+// (the names of later releases' c_api/induced_subgraph.cpp and c_api/extract_ego.cpp; subgraph.hip)
+extern "C" cugraph_error_code_t cugraph_extract_induced_subgraph(
+  const cugraph_resource_handle_t* handle,
+  cugraph_graph_t* graph,
+  const cugraph_type_erased_device_array_view_t* subgraph_offsets,
+  const cugraph_type_erased_device_array_view_t* subgraph_vertices,
+  bool_t do_expensive_check,
+  cugraph_induced_subgraph_result_t** result,
+  cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  (void)do_expensive_check;  // the lookup finds an unknown id and the sort a repeated one either way
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED,
+                "multi-GPU extract_induced_subgraph is not implemented in this build");
+    CGX_INPUT(subgraph_offsets != nullptr && subgraph_vertices != nullptr,
+              "Invalid input argument: subgraph_offsets or subgraph_vertices is NULL");
+    auto const& off = *AV(subgraph_offsets);
+    auto const& ver = *AV(subgraph_vertices);
+    CGX_INPUT(off.type == INT64, "Invalid input argument: subgraph_offsets must be INT64");
+    CGX_INPUT(off.size >= 1, "Invalid input argument: subgraph_offsets needs at least one entry");
+    CGX_INPUT(ver.type == g.vertex_type, "vertex type of graph and subgraph_vertices must match");
+    auto res = std::make_unique<induced_subgraph_result_t>();
+    run_induced_subgraph(*H(handle), g, off, ver, *res);
+    HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
+    *result = reinterpret_cast<cugraph_induced_subgraph_result_t*>(res.release());
+  });
+}
+
+extern "C" cugraph_error_code_t cugraph_extract_ego(const cugraph_resource_handle_t* handle,
+                                                   cugraph_graph_t* graph,
+                                                   const cugraph_type_erased_device_array_view_t* source_vertices,
+                                                   size_t radius,
+                                                   bool_t do_expensive_check,
+                                                   cugraph_induced_subgraph_result_t** result,
+                                                   cugraph_error_t** error)
+{
+  *result = nullptr;
+  *error  = nullptr;
+  (void)do_expensive_check;  // the lookup finds an unknown id either way
+  return guarded(error, [&] {
+    CGX_EXPECTS(handle != nullptr, CUGRAPH_INVALID_HANDLE, "invalid resource handle");
+    CGX_INPUT(graph != nullptr, "Invalid input argument: graph is NULL");
+    auto& g = *G(graph);
+    CGX_EXPECTS(!g.multi_gpu, CUGRAPH_NOT_IMPLEMENTED, "multi-GPU extract_ego is not implemented in this build");
+    CGX_INPUT(source_vertices != nullptr, "Invalid input argument: source_vertices is NULL");
+    auto const& src = *AV(source_vertices);
+    CGX_INPUT(src.type == g.vertex_type, "vertex type of graph and source_vertices must match");
+    auto res = std::make_unique<induced_subgraph_result_t>();
+    run_extract_ego(*H(handle), g, src, radius, *res);
     HIP_CHECK(hipStreamSynchronize(H(handle)->stream));
     *result = reinterpret_cast<cugraph_induced_subgraph_result_t*>(res.release());
   });

@@ -607,6 +607,20 @@ extern "C" cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t
       CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: kt_path must be 0, 1 or 2");
       i32(t.kt_path);
     }
+    else if (n == "sg_path") {
+      CGX_INPUT(value == 0 || value == 1 || value == 2, "Invalid input argument: sg_path must be 0, 1 or 2");
+      i32(t.sg_path);
+    }
+    else if (n == "sg_split_min") {
+      CGX_INPUT(value >= 1 && value == (double)(int64_t)value,
+                "Invalid input argument: sg_split_min must be an integer, at least 1");
+      t.sg_split_min = (int64_t)value;
+    }
+    else if (n == "ego_budget") {
+      CGX_INPUT(value >= 1 && value == (double)(int64_t)value,
+                "Invalid input argument: ego_budget must be an integer, at least 1");
+      t.ego_budget = (int64_t)value;
+    }
     else if (n == "bfs_alpha") t.bfs_alpha = value;
     else if (n == "bfs_beta") t.bfs_beta = value;
     else if (n == "mg_bfs_alpha") t.mg_bfs_alpha = value;

@@ -481,6 +481,145 @@ def k_truss(G, k):
     return res
 
 
+def _check_radius(radius, center, undirected, distance):
+    """The argument checks of ego_graph / batched_ego_graphs, before any GPU call."""
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or radius < 0:
+        raise ValueError(f"'radius' must be a non-negative integer, got: {radius}")
+    if center is not True:
+        raise NotImplementedError("center=False is not supported")
+    if undirected is not False:
+        raise NotImplementedError("undirected=True is not supported")
+    if distance is not None:
+        raise NotImplementedError("distance is not supported: distances are counted in hops")
+
+
+def _vertex_list(G, nxv, vertices, what):
+    """``vertices`` (a scalar, a list, an array, a Series or a one-column frame) as an int64 numpy
+    array of G's ids; NetworkX labels go through the view's index."""
+    if hasattr(vertices, "columns"):
+        if len(vertices.columns) != 1:
+            raise ValueError("multi-column vertex ids are not supported by this build")
+        vertices = vertices[vertices.columns[0]]
+    if hasattr(vertices, "to_numpy"):
+        vertices = vertices.to_numpy()
+    if isinstance(vertices, np.ndarray):
+        vertices = vertices.tolist()
+    elif hasattr(vertices, "cpu") and hasattr(vertices, "numpy"):
+        vertices = vertices.cpu().numpy().tolist()
+    elif np.isscalar(vertices) or not hasattr(vertices, "__len__"):
+        vertices = [vertices]
+    vertices = list(vertices)
+    if nxv is not None:
+        vertices = nxv.ids(vertices)
+    for v in vertices:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"'{what}' must hold integer vertex ids, got: {v!r}")
+    return np.asarray(vertices, dtype=np.int64)
+
+
+def _subgraph_input(G, api):
+    """(NetworkX view or None, Graph) with the distributed graph refused."""
+    nxv = None
+    if _is_nx(G):
+        nxv = _NxView(G)
+        G = nxv.G
+    if G.is_distributed():
+        raise NotImplementedError(f"{api} of a distributed graph is not implemented in this build")
+    return nxv, G
+
+
+def _extract(G, ids, offsets, radius):
+    """The four host arrays (src, dst, weights or None, offsets) of the induced subgraphs
+    (``offsets`` given) or the ego nets (``radius`` given) of ``ids``."""
+    import torch
+    if G.edgelist is None or G._plc_graph is None:
+        if len(ids):
+            raise ValueError("A provided vertex was not valid")
+        n = 1 if offsets is None else len(offsets)
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), None, np.zeros(n, np.int64)
+    p = _plc()
+    dev = torch.as_tensor(ids).to(_vertex_dtype(G)).cuda()
+    if offsets is not None:
+        out = p.induced_subgraph(p.ResourceHandle(), G._plc_graph, dev, torch.as_tensor(offsets).cuda(), False)
+    else:
+        out = p.ego_graph(p.ResourceHandle(), G._plc_graph, dev, int(radius), False)
+    src, dst, w, off = out
+    return src.cpu().numpy(), dst.cpu().numpy(), (None if w is None else w.cpu().numpy()), off.cpu().numpy()
+
+
+def _edges_to_graph(G, nxv, nx_directed, src, dst, w):
+    """One extracted edge list as a Graph of G's type, or as a NetworkX graph with the view's labels."""
+    import pandas as pd
+    if nxv is not None:
+        import networkx as nx
+        res = nx.DiGraph() if nx_directed else nx.Graph()
+        labels_s, labels_d = nxv.label(src), nxv.label(dst)
+        if w is None:
+            res.add_edges_from(zip(labels_s, labels_d))
+        else:
+            res.add_weighted_edges_from(zip(labels_s, labels_d, w.tolist()))
+        return res
+    out = type(G)(directed=G.is_directed()) if type(G) is Graph else type(G)()
+    if len(src):
+        cols = {"src": src, "dst": dst}
+        if w is not None:
+            cols["weights"] = w
+        out.from_pandas_edgelist(pd.DataFrame(cols), "src", "dst", "weights" if w is not None else None,
+                                 renumber=G._renumber, store_transposed=G.store_transposed)
+    return out
+
+
+def subgraph(G, vertices):
+    """community/subgraph_extraction.py:22-87.  The subgraph of G induced by ``vertices`` (a list, an
+    array or a Series, in any order) as a Graph of G's type (a NetworkX graph for a NetworkX input),
+    with G's weights if it has them, built with G's ``renumber`` / ``store_transposed``.  Every stored
+    edge with both ends in the set is kept, self-loops included.  An empty set, or one without edges
+    inside, gives a graph without edges; a vertex G does not know, or one given twice, is a ValueError."""
+    nx_directed = _is_nx(G) and G.is_directed()
+    nxv, G = _subgraph_input(G, "subgraph")
+    ids = _vertex_list(G, nxv, vertices, "vertices")
+    src, dst, w, _ = _extract(G, ids, np.asarray([0, len(ids)], np.int64), None)
+    return _edges_to_graph(G, nxv, nx_directed, src, dst, w)
+
+
+def ego_graph(G, n, radius=1, center=True, undirected=False, distance=None):
+    """community/egonet.py:47-113.  The subgraph induced by every vertex within ``radius`` hops of ``n``
+    (over out-edges for a directed graph), ``n`` included, as a Graph of G's type or a NetworkX graph
+    for a NetworkX input; weights are carried.  ``center=False``, ``undirected=True`` and a
+    ``distance`` key, which the reference documents as unsupported and ignores, raise
+    NotImplementedError here."""
+    _check_radius(radius, center, undirected, distance)
+    nx_directed = _is_nx(G) and G.is_directed()
+    nxv, G = _subgraph_input(G, "ego_graph")
+    ids = _vertex_list(G, nxv, n, "n")[:1]
+    if len(ids) != 1:
+        raise ValueError("'n' must be one vertex")
+    src, dst, w, _ = _extract(G, ids, None, radius)
+    return _edges_to_graph(G, nxv, nx_directed, src, dst, w)
+
+
+def batched_ego_graphs(G, seeds, radius=1, center=True, undirected=False, distance=None):
+    """community/egonet.py:116-177.  The ego nets of every seed at once.  Returns (DataFrame with
+    'src', 'dst' and, for a weighted graph, 'weight'; Series of len(seeds) + 1 offsets): the edges of
+    seed i's ego net are the rows [offsets[i], offsets[i + 1]).  For a NetworkX input the frame holds
+    the NetworkX labels and the offsets are a list, as in the reference.  A seed may repeat; no seeds
+    give an empty frame and the offsets [0].  The unsupported keywords raise as in ``ego_graph``."""
+    import pandas as pd
+    _check_radius(radius, center, undirected, distance)
+    nxv, G = _subgraph_input(G, "batched_ego_graphs")
+    ids = _vertex_list(G, nxv, seeds, "seeds")
+    src, dst, w, off = _extract(G, ids, None, radius)
+    if nxv is not None:
+        src, dst = nxv.label(src), nxv.label(dst)
+    cols = {"src": src, "dst": dst}
+    if w is not None:
+        cols["weight"] = w
+    df = pd.DataFrame(cols)
+    if nxv is not None:
+        return df, off.tolist()
+    return df, pd.Series(off)
+
+
 def _similarity(G, vertex_pair, measure):
     """link_prediction/jaccard.py:21-134 and its siblings, for one of 'jaccard', 'sorensen',
     'overlap'."""

@@ -9,7 +9,8 @@ hot path: ``ResourceHandle`` (resource_handle.pyx:25-46), ``GraphProperties``
 (weakly_connected_components.pyx, components/_connectivity.pyx:132-220), ``triangle_count``
 (triangle_count.pyx:57-60), ``core_number`` (core_number.pyx:58-140), ``k_core`` (the C
 entry of core_algorithms.h), ``k_truss_subgraph`` (the signature of later pylibcugraph releases;
-22.10 reaches its legacy k-truss from cugraph only), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
+22.10 reaches its legacy k-truss from cugraph only), ``induced_subgraph`` / ``ego_graph`` (likewise the
+signatures of later releases), ``jaccard_coefficients`` / ``sorensen_coefficients`` /
 ``overlap_coefficients`` (jaccard_coefficients.pyx:58-150 and its siblings) and
 ``get_two_hop_neighbors`` (the C entry of graph_functions.h), ``uniform_neighbor_sample``
 (uniform_neighbor_sample.pyx), ``uniform_random_walks`` / ``biased_random_walks`` (uniform_random_walks.pyx) and
@@ -33,7 +34,8 @@ __all__ = ["trim_device_cache", "ResourceHandle", "GraphProperties", "SGGraph", 
            "personalized_pagerank", "katz_centrality", "eigenvector_centrality", "betweenness_centrality",
            "edge_betweenness_centrality", "hits", "bfs", "sssp",
            "louvain", "weakly_connected_components", "strongly_connected_components", "triangle_count",
-           "core_number", "k_core", "k_truss_subgraph", "jaccard_coefficients", "sorensen_coefficients",
+           "core_number", "k_core", "k_truss_subgraph", "induced_subgraph", "ego_graph", "jaccard_coefficients",
+           "sorensen_coefficients",
            "overlap_coefficients",
            "get_two_hop_neighbors", "uniform_neighbor_sample", "uniform_random_walks", "biased_random_walks",
            "node2vec", "version"]
@@ -638,6 +640,52 @@ def k_truss_subgraph(resource_handle, graph, k, do_expensive_check):
         ptrs.append(w)
     out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_induced_subgraph_result_free)
     return out[0], out[1], (out[3] if w else None), out[2]
+
+
+def _subgraph_result(h, res):
+    ptrs = [_lib.lib.cugraph_induced_subgraph_get_sources(res), _lib.lib.cugraph_induced_subgraph_get_destinations(res),
+            _lib.lib.cugraph_induced_subgraph_get_subgraph_offsets(res)]
+    w = _lib.lib.cugraph_induced_subgraph_get_edge_weights(res)
+    if w:
+        ptrs.append(w)
+    out = views_to_tensors_owned(h, ptrs, res, _lib.lib.cugraph_induced_subgraph_result_free)
+    return out[0], out[1], (out[3] if w else None), out[2]
+
+
+def induced_subgraph(resource_handle, graph, subgraph_vertices, subgraph_offsets, do_expensive_check):
+    """C entry cugraph_extract_induced_subgraph (graph_functions.h; the name, argument order and return
+    tuple of later pylibcugraph releases).  ``subgraph_vertices``: the vertex sets back to back, in the
+    graph's vertex type and in any order inside a set; ``subgraph_offsets``: int64, sets + 1 entries, set
+    ``i`` is ``subgraph_vertices[subgraph_offsets[i]:subgraph_offsets[i + 1]]``.  Returns (sources,
+    destinations, edge_weights or None, subgraph_offsets): for every set the stored edges with both ends
+    in it (loops and every copy of a repeated edge included), sets in the order given, edges by ascending
+    internal source id and then stored order; the int64 offsets give each set's range.  ValueError: bad
+    offsets, an id the graph does not know, a vertex repeated inside a set."""
+    import torch
+    h = resource_handle.ptr
+    verts = DeviceView(subgraph_vertices)
+    offs = DeviceView(subgraph_offsets, torch.int64)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_extract_induced_subgraph", h, graph.c_graph_ptr, offs.ptr, verts.ptr,
+              int(bool(do_expensive_check)), ctypes.byref(res))
+    return _subgraph_result(h, res)
+
+
+def ego_graph(resource_handle, graph, source_vertices, radius, do_expensive_check):
+    """C entry cugraph_extract_ego (community_algorithms.h; the name, argument order and return tuple of
+    later pylibcugraph releases).  Returns (sources, destinations, edge_weights or None, subgraph_offsets)
+    as ``induced_subgraph`` does, subgraph ``i`` induced by every vertex within ``radius`` hops over
+    out-edges of ``source_vertices[i]``, the source included.  A source may repeat; no sources give no
+    edges and the offsets [0].  ValueError: an id the graph does not know, a radius that is not a
+    non-negative integer."""
+    if isinstance(radius, bool) or int(radius) != radius or int(radius) < 0:
+        raise ValueError(f"'radius' must be a non-negative integer, got: {radius}")
+    h = resource_handle.ptr
+    src = DeviceView(source_vertices)
+    res = ctypes.c_void_p()
+    _lib.call("cugraph_extract_ego", h, graph.c_graph_ptr, src.ptr, int(radius), int(bool(do_expensive_check)),
+              ctypes.byref(res))
+    return _subgraph_result(h, res)
 
 
 def _similarity(api, resource_handle, graph, first, second, use_weight, do_expensive_check):

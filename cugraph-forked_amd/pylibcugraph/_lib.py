@@ -141,6 +141,8 @@ _proto("cugraph_k_core_result_get_dst_vertices", P, P)
 _proto("cugraph_k_core_result_get_weights", P, P)
 _proto("cugraph_k_core_result_free", None, P)
 _proto("cugraph_k_truss_subgraph", c_int, P, P, c_size_t, c_int, PP, PP)
+_proto("cugraph_extract_induced_subgraph", c_int, P, P, P, P, c_int, PP, PP)
+_proto("cugraph_extract_ego", c_int, P, P, P, c_size_t, c_int, PP, PP)
 _proto("cugraph_induced_subgraph_get_sources", P, P)
 _proto("cugraph_induced_subgraph_get_destinations", P, P)
 _proto("cugraph_induced_subgraph_get_edge_weights", P, P)

@@ -145,12 +145,20 @@ size_t cugraph_amd_last_iterations(const cugraph_resource_handle_t* handle);
  * segments of that many, a wave each; a multiple of 64, at least 64, default 2048; neither option changes a bit
  * of a vertex score, and bc_row_split none of an edge score), kt_path (k-truss: 0 a frontier edge of the peel and
  * an edge of the support pass go to a thread, a wave or the split tier by their row sizes | 1 always a thread |
- * 2 always a wave; the result, its order included, is the same under all three); "defaults" resets them all.  Booleans
+ * 2 always a wave; the result, its order included, is the same under all three), sg_path (induced subgraphs and ego
+ * nets: 0 the row of a (subgraph, member vertex) goes to a thread, a wave or the split tier by its length | 1 always
+ * a thread | 2 always a wave), sg_split_min (the same extraction: a row of at least this many entries is cut into
+ * segments of 1024 entries, a wave each; an integer, at least 1, default 64; read with sg_path 0 only),
+ * ego_budget (ego nets: candidate keys expanded and sorted per batch of whole sources' hops, a source whose hop
+ * alone exceeds it goes through a V-bit map; an integer, at least 1, default 2^26); the three change no byte of a
+ * result, its order included; "defaults" resets them all.  Booleans
  * are 0 / 1.  Unknown names: CUGRAPH_INVALID_INPUT.
  */
 cugraph_error_code_t cugraph_amd_set_option(cugraph_resource_handle_t* handle, const char* name, double value,
                                             cugraph_error_t** error);
 double cugraph_amd_last_hot_kernel_ms(const cugraph_resource_handle_t* handle);
+/* After cugraph_extract_induced_subgraph / cugraph_extract_ego, with or without profiling: the segments the
+ * extraction's split tier cut hub rows into (0: no row went there). */
 size_t cugraph_amd_last_hot_kernel_launches(const cugraph_resource_handle_t* handle);
 /* PageRank (single GPU): the push schedule of the last call -- its packed 16-bit stream entries (jumps and
  * padding included; 0 for 32-bit entries or the pull path) and the vertices whose x~ its layout map moves

@@ -98,6 +98,33 @@ cugraph_error_code_t cugraph_k_truss_subgraph(const cugraph_resource_handle_t* h
                                               cugraph_induced_subgraph_result_t** result,
                                               cugraph_error_t** error);
 
+/*
+ * Ego nets (the name and signature of later cuGraph releases; the 22.10 reference reaches
+ * community/legacy/egonet.cu from Python only).  Kernels: csrc/subgraph.hip.
+ *
+ * Subgraph i is the subgraph induced (cugraph_extract_induced_subgraph, graph_functions.h: the same edges,
+ * order and offsets) by every vertex reachable from source_vertices[i] over out-edges in at most radius
+ * hops, the source included.  radius 0 gives the source's self-loops and nothing else; a radius above the
+ * eccentricity gives the whole reachable set.  source_vertices holds external ids in the graph's vertex
+ * type; a source may appear more than once and each occurrence gets its own, identical, subgraph.  An
+ * empty source_vertices gives an empty result whose offsets are {0} (the reference refuses it).
+ *
+ * The sets of all sources grow together, a hop at a time, in batches of at most the handle option
+ * ego_budget candidate keys; the result is the same bytes from call to call and under every value of
+ * ego_budget, sg_path and sg_split_min.
+ *
+ * CUGRAPH_INVALID_INPUT: graph or source_vertices NULL, a type mismatch, an id the graph does not know
+ * (with or without do_expensive_check).  CUGRAPH_NOT_IMPLEMENTED: a multi-GPU graph, or sources x vertices
+ * above 64 bits.  *result is NULL on error.
+ */
+cugraph_error_code_t cugraph_extract_ego(const cugraph_resource_handle_t* handle,
+                                         cugraph_graph_t* graph,
+                                         const cugraph_type_erased_device_array_view_t* source_vertices,
+                                         size_t radius,
+                                         bool_t do_expensive_check,
+                                         cugraph_induced_subgraph_result_t** result,
+                                         cugraph_error_t** error);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,13 +80,45 @@ cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_edge_weigh
   cugraph_induced_subgraph_result_t* induced_subgraph);
 
 /*
- * Two size_t values {0, number of edges}: the one subgraph's range in the three arrays.  data_type_id_t
- * of this ABI has no SIZE_T, so the view's type id is INT64 (the same 8 bytes).
+ * Number of subgraphs + 1 size_t values: subgraph i is the range [offsets[i], offsets[i + 1]) of the three
+ * arrays ({0, number of edges} for the one subgraph of k-truss).  data_type_id_t of this ABI has no SIZE_T,
+ * so the view's type id is INT64 (the same 8 bytes).
  */
 cugraph_type_erased_device_array_view_t* cugraph_induced_subgraph_get_subgraph_offsets(
   cugraph_induced_subgraph_result_t* induced_subgraph);
 
 void cugraph_induced_subgraph_result_free(cugraph_induced_subgraph_result_t* induced_subgraph);
+
+/*
+ * The subgraphs induced by vertex sets (the name and signature of later cuGraph releases; the 22.10
+ * reference has no C entry, its C++ is structure/induced_subgraph_impl.cuh).  Kernels: csrc/subgraph.hip.
+ *
+ * subgraph_offsets: INT64, number of subgraphs + 1 entries (at least 1); it starts at 0, does not decrease
+ * and ends at the size of subgraph_vertices.  subgraph_vertices: external ids in the graph's vertex type;
+ * set i is the range [subgraph_offsets[i], subgraph_offsets[i + 1]).  The vertices of a set may come in any
+ * order (the reference wants them sorted; the entry sorts each set by internal id itself) and a set may be
+ * empty.
+ *
+ * Subgraph i holds every stored edge (u, v) of the out-edge orientation with u and v both in set i, with
+ * its weight when the graph has weights: a self-loop of a member is such an edge, a repeated edge of a
+ * multigraph comes back as often as it is stored, and both directions of an undirected edge come back.
+ * Subgraphs appear in the order given; inside one, edges ascend by the internal id of the source and keep
+ * the stored row order within a source.  The result is the same bytes from call to call and under every
+ * value of the handle options sg_path and sg_split_min.
+ *
+ * CUGRAPH_INVALID_INPUT: graph or a view NULL, offsets that break the rules above, a type mismatch, an id
+ * the graph does not know, a vertex repeated inside one set -- with or without do_expensive_check, which
+ * adds nothing.  CUGRAPH_NOT_IMPLEMENTED: a multi-GPU graph, or subgraphs x vertices above 64 bits.
+ * *result is NULL on error.
+ */
+cugraph_error_code_t cugraph_extract_induced_subgraph(
+  const cugraph_resource_handle_t* handle,
+  cugraph_graph_t* graph,
+  const cugraph_type_erased_device_array_view_t* subgraph_offsets,
+  const cugraph_type_erased_device_array_view_t* subgraph_vertices,
+  bool_t do_expensive_check,
+  cugraph_induced_subgraph_result_t** result,
+  cugraph_error_t** error);
 
 #ifdef __cplusplus
 }
