@@ -62,12 +62,6 @@ constexpr int32_t kBcNoLevel = -2; // stands for the level of an entry that is n
 enum { BC_DISCOVER = 0, BC_COUNT = 1, BC_BACK = 2 };
 
 template <typename T>
-__device__ __forceinline__ T bc_ld(T const* p)
-{
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <typename T>
 __device__ __forceinline__ void bc_st(T* p, T v)
 {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -134,7 +128,7 @@ __device__ __forceinline__ double bc_block(bc_args<V, E> const& a, bool mine, do
       p[u] = (size_t)w[u] * (size_t)a.nb + (size_t)lane;  // read by lanes below nb only (mine)
     }
 #pragma unroll
-    for (int u = 0; u < kBcAhead; ++u) dd[u] = (mine && t0 + u < cnt) ? bc_ld(a.dist + p[u]) : kBcNoLevel;
+    for (int u = 0; u < kBcAhead; ++u) dd[u] = (mine && t0 + u < cnt) ? ld_relaxed(a.dist + p[u]) : kBcNoLevel;
     if constexpr (PH == BC_DISCOVER) {
 #pragma unroll
       for (int u = 0; u < kBcAhead; ++u) {
@@ -143,7 +137,7 @@ __device__ __forceinline__ double bc_block(bc_args<V, E> const& a, bool mine, do
         // below shows that the vertex is listed already
         bool const stored = dd[u] == -1;
         if (stored) bc_st(a.dist + p[u], (int32_t)a.d);
-        if (__ballot(stored) && lane == 0 && bc_ld(a.stamp + w[u]) != a.stamp_id &&
+        if (__ballot(stored) && lane == 0 && ld_relaxed(a.stamp + w[u]) != a.stamp_id &&
             __hip_atomic_exchange(a.stamp + w[u], a.stamp_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) !=
               a.stamp_id) {
           unsigned long long const pos =

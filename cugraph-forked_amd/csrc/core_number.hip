@@ -51,9 +51,10 @@
 // segments.  List appends cost one counter add per wave.
 //
 // k-core: core numbers per internal id (computed here, or scattered from the caller's result),
-// a count pass per row (a thread per light row, a wave per longer one), a scan, a fill pass.
+// then row_extract.hpp's extraction with the test kcore_rows.
 #include "capi.hpp"
 #include "prims.hpp"
+#include "row_extract.hpp"
 
 #include <algorithm>
 #include <limits>
@@ -107,22 +108,6 @@ struct core_args {
   int compact;  // tuning_t::core_scan
 };
 
-template <typename T>
-__device__ __forceinline__ T ld(T const* p)
-{
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ long long wave_max_ll(long long v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    long long const t = __shfl_xor(v, o, 64);
-    v                 = t > v ? t : v;
-  }
-  return v;
-}
-
 template <typename E>
 __device__ __forceinline__ void publish_min(E* slot, E mn)
 {
@@ -133,27 +118,6 @@ __device__ __forceinline__ void publish_min(E* slot, E mn)
   }
   if ((threadIdx.x & 63) == 0 && mn != std::numeric_limits<E>::max())
     __hip_atomic_fetch_min(slot, mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// list[count ..) gets the flagged lanes' values, one counter add per wave.  Every lane of the
-// wave must call it.
-template <typename V>
-__device__ __forceinline__ void wave_append(V* list, unsigned long long* count, unsigned long long cap, int* bad,
-                                            bool flag, V value)
-{
-  unsigned long long const m = __ballot(flag);
-  if (!m) return;  // wave-uniform
-  int const lane   = threadIdx.x & 63;
-  int const leader = __ffsll((long long)m) - 1;
-  unsigned long long base = 0;
-  if (lane == leader)
-    base = __hip_atomic_fetch_add(count, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  base = __shfl(base, leader, 64);
-  if (flag) {
-    unsigned long long const pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-    if (pos < cap) list[pos] = value;
-    else atomicOr(bad, 1);
-  }
 }
 
 // ---------------------------------------------------------------- degrees
@@ -248,9 +212,9 @@ __global__ __launch_bounds__(kCoreBlock) void k_core_scan(core_args<V, E> a)
       in_r      = d > k;  // (peeled and isolated vertices are below k)
       if (in_r && d < mn) mn = d;
     }
-    wave_append(a.front[fp], &st->nf[fp], (unsigned long long)a.nv, &st->bad, in_f, v);
+    list_append_if(a.front[fp], &st->nf[fp], (unsigned long long)a.nv, &st->bad, in_f, v);
     if (a.compact) {
-      wave_append(a.rem[rp ^ 1], &st->nr[rp ^ 1], (unsigned long long)a.nv, &st->bad, in_r, v);
+      list_append_if(a.rem[rp ^ 1], &st->nr[rp ^ 1], (unsigned long long)a.nv, &st->bad, in_r, v);
     } else {
       unsigned long long const m = __ballot(in_r);
       if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1)
@@ -269,7 +233,7 @@ __device__ __forceinline__ bool peel_entry(core_args<V, E> const& a, E k, V v, l
   u = a.idx[j];
   if (u == v || (j > b && a.idx[j - 1] == u)) return false;
   E* const p = a.deg + u;
-  if (ld(p) <= k) return false;
+  if (ld_relaxed(p) <= k) return false;
   E const old = __hip_atomic_fetch_sub(p, a.delta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (old == k + a.delta) return true;
   if (old <= k) __hip_atomic_fetch_add(p, a.delta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -309,10 +273,10 @@ __global__ __launch_bounds__(kCoreBlock) void k_core_peel(core_args<V, E> a)
       V u      = 0;
       bool hit = false;
       if (light && t < len) hit = peel_entry(a, k, v, b, b + t, u, mn);
-      wave_append(next, nnext, cap, &st->bad, hit, u);
+      list_append_if(next, nnext, cap, &st->bad, hit, u);
     }
-    wave_append(a.mids, &st->nmid, a.mid_cap, &st->bad, len >= kCoreWaveRow && len < kCoreHubRow, v);
-    wave_append(a.hubs, &st->nhub, a.hub_cap, &st->bad, len >= kCoreHubRow, v);
+    list_append_if(a.mids, &st->nmid, a.mid_cap, &st->bad, len >= kCoreWaveRow && len < kCoreHubRow, v);
+    list_append_if(a.hubs, &st->nhub, a.hub_cap, &st->bad, len >= kCoreHubRow, v);
   }
   publish_min(&st->mindeg, mn);
 }
@@ -344,7 +308,7 @@ __global__ __launch_bounds__(kCoreBlock) void k_core_peel_waves(core_args<V, E> 
       V u               = 0;
       bool hit          = false;
       if (j < e) hit = peel_entry(a, k, v, b, j, u, mn);
-      wave_append(next, nnext, cap, &st->bad, hit, u);
+      list_append_if(next, nnext, cap, &st->bad, hit, u);
     }
   }
   publish_min(&st->mindeg, mn);
@@ -378,7 +342,7 @@ __global__ __launch_bounds__(kCoreBlock) void k_core_peel_hubs(core_args<V, E> a
         V u               = 0;
         bool hit          = false;
         if (j < s1) hit = peel_entry(a, k, v, b, j, u, mn);
-        wave_append(next, nnext, cap, &st->bad, hit, u);
+        list_append_if(next, nnext, cap, &st->bad, hit, u);
       }
     }
   }
@@ -522,65 +486,20 @@ __device__ __forceinline__ bool kcore_keep(V const* idx, E const* cn, unsigned l
   return (unsigned long long)cn[u] >= k;
 }
 
-// The kept entries of every row (both endpoints at core k or above, no loops, no repeats): counted
-// into cnt[v] (pos == nullptr) or written in row order from pos[v] on.  A thread per light row, a
-// wave per row from kCoreWaveRow entries.  The 256 rows of a block lie gridDim.x apart: on a
-// degree-sorted adjacency the longest rows are the first ones and so go to different blocks.
-template <typename V, typename E, typename W>
-__global__ __launch_bounds__(kCoreBlock) void k_kcore_rows(E const* off, V const* idx, W const* w, int64_t nv,
-                                                          E const* cn, unsigned long long k, E const* pos, E* cnt,
-                                                          V* src, V* dst, W* wout)
-{
-  int const tid = threadIdx.x, lane = tid & 63;
-  int64_t const apart = (int64_t)gridDim.x;
-  for (int64_t base = 0; base < nv; base += apart * kCoreBlock) {
-    int64_t const v = base + tid * apart + blockIdx.x;
-    long long b = 0, e = 0;
-    bool in = false;
-    if (v < nv) {
-      b  = (long long)off[v];
-      e  = (long long)off[v + 1];
-      in = (unsigned long long)cn[v] >= k;
-    }
-    long long const len = in ? e - b : 0;
-    if (v < nv && len < kCoreWaveRow) {
-      long long c = 0;
-      long long const p0 = pos ? (long long)pos[v] : 0;
-      for (long long j = b; j < b + len; ++j) {
-        if (!kcore_keep(idx, cn, k, v, b, j)) continue;
-        if (pos) {
-          src[p0 + c] = (V)v;
-          dst[p0 + c] = idx[j];
-          if (wout) wout[p0 + c] = w[j];
-        }
-        ++c;
-      }
-      if (!pos) cnt[v] = (E)c;
-    }
-    unsigned long long m = __ballot(len >= kCoreWaveRow);
-    while (m) {  // wave-uniform
-      int const l = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      long long const bb = __shfl(b, l, 64), ee = __shfl(e, l, 64);
-      int64_t const vv   = base + (tid - lane + l) * apart + blockIdx.x;
-      long long c        = pos ? (long long)pos[vv] : 0;  // wave-uniform
-      long long const c0 = c;
-      for (long long j0 = bb; j0 < ee; j0 += 64) {
-        long long const j = j0 + lane;
-        bool const keep   = j < ee && kcore_keep(idx, cn, k, vv, bb, j);
-        unsigned long long const km = __ballot(keep);
-        if (pos && keep) {
-          long long const p = c + __popcll(km & ((1ull << lane) - 1ull));
-          src[p]            = (V)vv;
-          dst[p]            = idx[j];
-          if (wout) wout[p] = w[j];
-        }
-        c += __popcll(km);
-      }
-      if (!pos && lane == 0) cnt[vv] = (E)(c - c0);
-    }
+// row_extract.hpp's test: the rows of the core's vertices, their entries whose other end is in the
+// core too (no loops, no repeats); weights lie beside the entries
+template <typename V, typename E>
+struct kcore_rows {
+  V const* idx;
+  E const* cn;
+  unsigned long long k;
+  __device__ __forceinline__ bool row(int64_t v) const { return (unsigned long long)cn[v] >= k; }
+  __device__ __forceinline__ bool keep(int64_t v, long long b, long long j) const
+  {
+    return kcore_keep(idx, cn, k, v, b, j);
   }
-}
+  __device__ __forceinline__ long long wpos(long long j) const { return j; }
+};
 
 template <typename V, typename E, typename W>
 void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const* given, bool expensive,
@@ -588,11 +507,6 @@ void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const
 {
   hipStream_t s    = h.stream;
   int64_t const nv = g.num_vertices;
-  auto empty       = [&] {
-    res.src = std::make_unique<device_array_t>(0, g.vertex_type, s);
-    res.dst = std::make_unique<device_array_t>(0, g.vertex_type, s);
-    if (g.weighted) res.weights = std::make_unique<device_array_t>(0, g.weight_type, s);
-  };
   dbuf<E> cn;
   if (given) {
     // c_api/k_core.cpp: the core result's arrays are in the graph's types
@@ -603,8 +517,7 @@ void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const
   }
   if (nv == 0 || g.num_edges == 0) {
     reset_hot(h);
-    empty();
-    return;
+    return alloc_edge_arrays(g, 0, s, res.src, res.dst, res.weights);
   }
   adjacency_t& adj = ensure_adjacency(h, g, g.store_transposed);  // symmetric: either orientation
   cn.resize((size_t)nv, s);
@@ -629,30 +542,9 @@ void k_core_impl(handle_t& h, graph_t& g, size_t k, E delta, core_result_t const
   } else {
     core_numbers<V, E>(h, g, delta, expensive, cn.data());
   }
-  E const* off = adj.offsets.data<E>();
   V const* idx = adj.indices.data<V>();
-  W const* w   = g.weighted ? adj.weights.data<W>() : nullptr;
-  dbuf<E> cnt((size_t)nv + 1, s), pos((size_t)nv + 1, s);
-  HIP_CHECK(hipMemsetAsync(cnt.data() + nv, 0, sizeof(E), s));
-  unsigned const grid = grid_for((size_t)nv, kCoreBlock, 1u << 16);
-  hipLaunchKernelGGL((k_kcore_rows<V, E, W>), dim3(grid), dim3(kCoreBlock), 0, s, off, idx, w, nv, (E const*)cn.data(),
-                     (unsigned long long)k, (E const*)nullptr, cnt.data(), (V*)nullptr, (V*)nullptr, (W*)nullptr);
-  CGX_LAUNCH_CHECK();
-  exclusive_scan<E, E>(cnt.data(), pos.data(), (size_t)nv + 1, s);
-  size_t const total = (size_t)to_host_scalar(pos.data() + nv, s);  // the one read: the result's size
-  if (total == 0) {
-    empty();
-    return;
-  }
-  res.src = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  res.dst = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  if (g.weighted) res.weights = std::make_unique<device_array_t>(total, g.weight_type, s);
-  hipLaunchKernelGGL((k_kcore_rows<V, E, W>), dim3(grid), dim3(kCoreBlock), 0, s, off, idx, w, nv, (E const*)cn.data(),
-                     (unsigned long long)k, (E const*)pos.data(), (E*)nullptr, res.src->buf.data<V>(),
-                     res.dst->buf.data<V>(), g.weighted ? res.weights->buf.data<W>() : (W*)nullptr);
-  CGX_LAUNCH_CHECK();
-  unrenumber_int_to_ext(h, g, res.src->buf.data(), total);
-  unrenumber_int_to_ext(h, g, res.dst->buf.data(), total);
+  extract_rows(h, g, adj.offsets.data<E>(), idx, g.weighted ? adj.weights.data<W>() : (W const*)nullptr,
+               kcore_rows<V, E>{idx, cn.data(), (unsigned long long)k}, res.src, res.dst, res.weights);
 }
 
 }  // namespace

@@ -63,11 +63,11 @@
 // split tier.  Appends cost one counter add per group of lanes that arrive together (a wave in the
 // wave tiers).  Only vector stores and ordinary atomics are used.
 //
-// Extraction: a count pass per row over the positions whose edge is alive, a scan, a fill pass (the
-// shape of core_number.hip's k_kcore_rows); external ids through the number map.
+// Extraction: row_extract.hpp over the positions whose edge is alive (kt_rows).
 #include "capi.hpp"
 #include "intersect.hpp"
 #include "prims.hpp"
+#include "row_extract.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -77,7 +77,6 @@ namespace cgx {
 namespace {
 
 constexpr int kKtBlock        = kIsectBlock;
-constexpr int kKtWaveRow      = 64;    // extraction: rows with at least this many entries take a wave
 constexpr int kKtSplitMin     = 1024;  // an edge whose shorter row has this many entries or more: the split tier
 constexpr int kKtSegBits      = 39;    // heavy word: segments in the low bits (sim_seg_len), list position above
 constexpr int kKtGridPerCu    = 8;
@@ -119,29 +118,6 @@ struct kt_args {
   int path;       // tuning_t::kt_path
   int split;      // the split tier is on
 };
-
-template <typename T>
-__device__ __forceinline__ T kt_ld(T const* p)
-{
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// list[count ..) gets the calling lanes' values: one counter add per group of lanes that arrive together.
-// May be called under divergence; the lanes that call it are the ones the ballot sees.
-template <typename T>
-__device__ __forceinline__ void kt_append(T* list, unsigned long long* count, unsigned long long cap, int* bad, T value)
-{
-  unsigned long long const m = __ballot(1);
-  int const lane             = threadIdx.x & 63;
-  int const leader           = __ffsll((long long)m) - 1;
-  unsigned long long base    = 0;
-  if (lane == leader)
-    base = __hip_atomic_fetch_add(count, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  base = __shfl(base, leader, 64);
-  unsigned long long const pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-  if (pos < cap) list[pos] = value;
-  else atomicOr(bad, 1);
-}
 
 // ---------------------------------------------------------------- simple rows, edge ids
 // A wave per row: the entries that are neither the row's own vertex nor a repeat of the entry before
@@ -263,14 +239,14 @@ struct kt_tri {
     int const old = __hip_atomic_fetch_sub(sup + x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old == t) {
       __hip_atomic_store(round + x, r + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      kt_append(next, nnext, cap, bad, (E)x);
+      list_append(next, nnext, cap, bad, (E)x);
     }
   }
   template <typename V>
   __device__ __forceinline__ void operator()(V, long long i, long long j) const
   {
     long long const e1 = (long long)ea[i], e2 = (long long)eb[j];
-    unsigned const r1 = kt_ld(round + e1), r2 = kt_ld(round + e2);
+    unsigned const r1 = ld_relaxed(round + e1), r2 = ld_relaxed(round + e2);
     if (r1 - 1u < r - 1u || r2 - 1u < r - 1u) return;      // 0 < round < r: destroyed earlier
     if ((r1 == r && e1 < e) || (r2 == r && e2 < e)) return;  // another edge of this round acts
     if (r1 != r) drop(e1);
@@ -417,7 +393,7 @@ __global__ __launch_bounds__(kKtBlock) void k_kt_scan(kt_args<V, E> a)
   for (long long e = blockIdx.x * (long long)kKtBlock + threadIdx.x; e < a.m; e += (long long)gridDim.x * kKtBlock)
     if (a.sup[e] < a.t) {
       a.round[e] = 1u;
-      kt_append(a.front[0], &st->nf[0], (unsigned long long)a.m, &st->bad, (E)e);
+      list_append(a.front[0], &st->nf[0], (unsigned long long)a.m, &st->bad, (E)e);
     }
 }
 
@@ -440,63 +416,17 @@ __device__ __forceinline__ bool kt_alive(E const* eid, unsigned const* round, lo
   return !round || round[eid[j]] == 0u;
 }
 
-// The positions of every simple row whose edge is alive (round == nullptr: all of them): counted into
-// cnt[v] (pos == nullptr) or written in row order from pos[v] on.  A thread per light row, a wave per row
-// from kKtWaveRow entries; the 256 rows of a block lie gridDim.x apart (core_number.hip k_kcore_rows).
-// orig: the stored position of every entry of a cleaned copy (nullptr: the position itself).
-template <typename V, typename E, typename W>
-__global__ __launch_bounds__(kKtBlock) void k_kt_rows(E const* off, V const* idx, E const* orig, W const* w, int64_t nv,
-                                                     E const* eid, unsigned const* round, E const* pos, E* cnt,
-                                                     V* src, V* dst, W* wout)
-{
-  int const tid = threadIdx.x, lane = tid & 63;
-  int64_t const apart = (int64_t)gridDim.x;
-  for (int64_t base = 0; base < nv; base += apart * kKtBlock) {
-    int64_t const v = base + tid * apart + blockIdx.x;
-    long long b = 0, e = 0;
-    if (v < nv) {
-      b = (long long)off[v];
-      e = (long long)off[v + 1];
-    }
-    long long const len = e - b;
-    if (v < nv && len < kKtWaveRow) {
-      long long c        = 0;
-      long long const p0 = pos ? (long long)pos[v] : 0;
-      for (long long j = b; j < e; ++j) {
-        if (!kt_alive(eid, round, j)) continue;
-        if (pos) {
-          src[p0 + c] = (V)v;
-          dst[p0 + c] = idx[j];
-          if (wout) wout[p0 + c] = w[orig ? (long long)orig[j] : j];
-        }
-        ++c;
-      }
-      if (!pos) cnt[v] = (E)c;
-    }
-    unsigned long long m = __ballot(len >= kKtWaveRow);
-    while (m) {  // wave-uniform
-      int const l = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      long long const bb = __shfl(b, l, 64), ee = __shfl(e, l, 64);
-      int64_t const vv   = base + (tid - lane + l) * apart + blockIdx.x;
-      long long c        = pos ? (long long)pos[vv] : 0;  // wave-uniform
-      long long const c0 = c;
-      for (long long j0 = bb; j0 < ee; j0 += 64) {
-        long long const j = j0 + lane;
-        bool const keep   = j < ee && kt_alive(eid, round, j);
-        unsigned long long const km = __ballot(keep);
-        if (pos && keep) {
-          long long const p = c + __popcll(km & ((1ull << lane) - 1ull));
-          src[p]            = (V)vv;
-          dst[p]            = idx[j];
-          if (wout) wout[p] = w[orig ? (long long)orig[j] : j];
-        }
-        c += __popcll(km);
-      }
-      if (!pos && lane == 0) cnt[vv] = (E)(c - c0);
-    }
-  }
-}
+// row_extract.hpp's test: every simple row, its positions whose edge is alive (round == nullptr: all of
+// them).  orig: the stored position of every entry of a cleaned copy (nullptr: the position itself).
+template <typename E>
+struct kt_rows {
+  E const* eid;
+  unsigned const* round;
+  E const* orig;
+  __device__ __forceinline__ bool row(int64_t) const { return true; }
+  __device__ __forceinline__ bool keep(int64_t, long long, long long j) const { return kt_alive(eid, round, j); }
+  __device__ __forceinline__ long long wpos(long long j) const { return orig ? (long long)orig[j] : j; }
+};
 
 inline unsigned kt_grid() { return (unsigned)(std::max(device_cu_count(), 1) * kKtGridPerCu); }
 
@@ -616,22 +546,21 @@ void kt_impl(handle_t& h, graph_t& g, size_t k, induced_subgraph_result_t& res)
   hipStream_t s    = h.stream;
   int64_t const nv = g.num_vertices;
   reset_hot(h);
-  auto finish = [&](size_t total) {
-    if (total == 0) {
-      res.src = std::make_unique<device_array_t>(0, g.vertex_type, s);
-      res.dst = std::make_unique<device_array_t>(0, g.vertex_type, s);
-      if (g.weighted) res.weights = std::make_unique<device_array_t>(0, g.weight_type, s);
-    }
+  auto finish = [&](size_t total) {  // the one subgraph's offsets
     res.offsets = std::make_unique<device_array_t>(2, INT64, s);
     int64_t const two[2] = {0, (int64_t)total};
     HIP_CHECK(hipMemcpyAsync(res.offsets->buf.data(), two, sizeof(two), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));  // `two` is read by then
   };
-  if (nv == 0 || g.num_edges == 0) return finish(0);
+  auto empty = [&] {
+    alloc_edge_arrays(g, 0, s, res.src, res.dst, res.weights);
+    finish(0);
+  };
+  if (nv == 0 || g.num_edges == 0) return empty();
   adjacency_t& adj = ensure_adjacency(h, g, g.store_transposed);  // symmetric: either orientation
   kt_build<V, E>(h, g, adj);
   int64_t const m = adj.kt_edges;
-  if (m == 0) return finish(0);
+  if (m == 0) return empty();
   E const* off  = adj.kt_clean ? adj.offsets.data<E>() : adj.kt_off.data<E>();
   V const* idx  = adj.kt_clean ? adj.indices.data<V>() : adj.kt_idx.data<V>();
   E const* orig = adj.kt_clean ? nullptr : adj.kt_orig.data<E>();
@@ -698,27 +627,9 @@ void kt_impl(handle_t& h, graph_t& g, size_t k, induced_subgraph_result_t& res)
   }
 
   // ---- extraction
-  unsigned const* rd = k > 2 ? round.data() : nullptr;
-  W const* w         = g.weighted ? adj.weights.data<W>() : nullptr;
-  dbuf<E> cnt((size_t)nv + 1, s), pos((size_t)nv + 1, s);
-  HIP_CHECK(hipMemsetAsync(cnt.data() + nv, 0, sizeof(E), s));
-  unsigned const grid = grid_for((size_t)nv, kKtBlock, 1u << 16);
-  hipLaunchKernelGGL((k_kt_rows<V, E, W>), dim3(grid), dim3(kKtBlock), 0, s, off, idx, orig, w, nv, eid, rd,
-                     (E const*)nullptr, cnt.data(), (V*)nullptr, (V*)nullptr, (W*)nullptr);
-  CGX_LAUNCH_CHECK();
-  exclusive_scan<E, E>(cnt.data(), pos.data(), (size_t)nv + 1, s);
-  size_t const total = (size_t)to_host_scalar(pos.data() + nv, s);  // the result's size
-  if (total == 0) return finish(0);
-  res.src = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  res.dst = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  if (g.weighted) res.weights = std::make_unique<device_array_t>(total, g.weight_type, s);
-  hipLaunchKernelGGL((k_kt_rows<V, E, W>), dim3(grid), dim3(kKtBlock), 0, s, off, idx, orig, w, nv, eid, rd,
-                     (E const*)pos.data(), (E*)nullptr, res.src->buf.data<V>(), res.dst->buf.data<V>(),
-                     g.weighted ? res.weights->buf.data<W>() : (W*)nullptr);
-  CGX_LAUNCH_CHECK();
-  unrenumber_int_to_ext(h, g, res.src->buf.data(), total);
-  unrenumber_int_to_ext(h, g, res.dst->buf.data(), total);
-  finish(total);
+  kt_rows<E> const alive{eid, k > 2 ? round.data() : nullptr, orig};
+  finish(extract_rows(h, g, off, idx, g.weighted ? adj.weights.data<W>() : (W const*)nullptr, alive, res.src, res.dst,
+                      res.weights));
 }
 
 }  // namespace

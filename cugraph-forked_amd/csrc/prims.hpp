@@ -104,6 +104,47 @@ __device__ __forceinline__ long long wave_sum_ll(long long v)
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ long long wave_max_ll(long long v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    long long const t = __shfl_xor(v, o, 64);
+    v                 = t > v ? t : v;
+  }
+  return v;
+}
+
+// a relaxed agent-scope load: it sees what other workgroups' atomics left in *p and orders nothing
+template <typename T>
+__device__ __forceinline__ T ld_relaxed(T const* p)
+{
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// list[count ..) gets the calling lanes' values: one counter add per group of lanes that arrive together.
+// May be called under divergence; the lanes that call it are the ones the ballot sees.  A value past
+// `cap` is not stored and sets *bad.
+template <typename T>
+__device__ __forceinline__ void list_append(T* list, unsigned long long* count, unsigned long long cap, int* bad, T value)
+{
+  unsigned long long const m = __ballot(1);
+  int const lane             = threadIdx.x & 63;
+  int const leader           = __ffsll((long long)m) - 1;
+  unsigned long long base    = 0;
+  if (lane == leader)
+    base = __hip_atomic_fetch_add(count, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  base = __shfl(base, leader, 64);
+  unsigned long long const pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+  if (pos < cap) list[pos] = value;
+  else atomicOr(bad, 1);
+}
+// the same for code in which every lane arrives and the flagged ones have a value
+template <typename T>
+__device__ __forceinline__ void list_append_if(T* list, unsigned long long* count, unsigned long long cap, int* bad,
+                                               bool flag, T value)
+{
+  if (flag) list_append(list, count, cap, bad, value);
+}
 
 // Sum over a 256-thread block; result valid in thread 0.  Uses `sm` (>= 4 doubles).
 __device__ __forceinline__ double block_sum_256(double v, double* sm)

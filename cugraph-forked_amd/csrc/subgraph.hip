@@ -27,6 +27,7 @@
 #include "capi.hpp"
 #include "intersect.hpp"
 #include "prims.hpp"
+#include "row_extract.hpp"
 #include "subgraph_keys.hpp"
 
 #include <rocprim/device/device_merge.hpp>
@@ -437,9 +438,7 @@ unsigned sg_grid() { return (unsigned)std::max(device_cu_count(), 1) * kSgGridPe
 void sg_empty_result(handle_t& h, graph_t& g, size_t ns, induced_subgraph_result_t& res)
 {
   hipStream_t s = h.stream;
-  res.src = std::make_unique<device_array_t>(0, g.vertex_type, s);
-  res.dst = std::make_unique<device_array_t>(0, g.vertex_type, s);
-  if (g.weighted) res.weights = std::make_unique<device_array_t>(0, g.weight_type, s);
+  alloc_edge_arrays(g, 0, s, res.src, res.dst, res.weights);
   res.offsets = std::make_unique<device_array_t>(ns + 1, INT64, s);
   HIP_CHECK(hipMemsetAsync(res.offsets->buf.data(), 0, (ns + 1) * sizeof(long long), s));
 }
@@ -496,9 +495,7 @@ void sg_extract(handle_t& h, graph_t& g, sg_key_t const* keys, long long m, long
   cnt.free();
   size_t const total = (size_t)to_host_scalar(ooff.data() + m, s);
 
-  res.src = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  res.dst = std::make_unique<device_array_t>(total, g.vertex_type, s);
-  if (g.weighted) res.weights = std::make_unique<device_array_t>(total, g.weight_type, s);
+  alloc_edge_arrays(g, total, s, res.src, res.dst, res.weights);
   res.offsets = std::make_unique<device_array_t>(ns + 1, INT64, s);
   gather<long long, long long>(res.offsets->buf.data<long long>(), ooff.data(), soff, ns + 1, s);
   if (total == 0) return;
@@ -517,8 +514,7 @@ void sg_extract(handle_t& h, graph_t& g, sg_key_t const* keys, long long m, long
                        (long long const*)ooff.data(), out);
     CGX_LAUNCH_CHECK();
   }
-  unrenumber_int_to_ext(h, g, res.src->buf.data(), total);
-  unrenumber_int_to_ext(h, g, res.dst->buf.data(), total);
+  unrenumber_edge_arrays(h, g, *res.src, *res.dst, total);
 }
 
 char const* const kSgFitMsg =

@@ -26,6 +26,7 @@
 // giant's set is linked from that vertex's row (or was one of its first k entries).  The
 // guess can therefore only change the time taken, never a label.
 #include "capi.hpp"
+#include "prims.hpp"
 
 namespace cgx {
 
@@ -37,23 +38,17 @@ constexpr int kHubRow    = 1024;  // ... and from here on: listed, the whole gri
 constexpr int kHubSeg    = 1024;  // entries per block and step of a hub row
 constexpr int kHubBlocks = 2048;
 
-template <typename T>
-__device__ __forceinline__ T ld(T const* p)
-{
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // root of x, halving the path on the way: a non-root slot is lowered to its grandparent
 template <typename V>
 __device__ __forceinline__ V find(V* parent, V x)
 {
-  V q = ld(parent + x);
+  V q = ld_relaxed(parent + x);
   while (q != x) {
-    V g = ld(parent + q);
+    V g = ld_relaxed(parent + q);
     if (g == q) return q;
     __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     x = g;
-    q = ld(parent + x);
+    q = ld_relaxed(parent + x);
   }
   return x;
 }
@@ -103,7 +98,7 @@ template <typename V>
 __global__ __launch_bounds__(kWccBlock) void k_wcc_compress(int64_t nv, V* parent)
 {
   for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nv; v += (int64_t)gridDim.x * blockDim.x) {
-    V p = ld(parent + v);
+    V p = ld_relaxed(parent + v);
     if (p == (V)v) continue;
     V r = find(parent, p);
     // atomic min, not a store: another thread's halving may still lower this slot to an
@@ -161,7 +156,7 @@ __global__ __launch_bounds__(kWccBlock) void k_wcc_link_rows(E const* off, V con
     if (v < nv) {
       b = (long long)off[v] + k;
       e = (long long)off[v + 1];
-      if (giant && ld(parent + v) == g0) e = b;  // in the giant's set: nothing to do
+      if (giant && ld_relaxed(parent + v) == g0) e = b;  // in the giant's set: nothing to do
     }
     long long const rem = e > b ? e - b : 0;
     if (rem > 0 && rem < kWaveRow) {

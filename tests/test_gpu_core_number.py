@@ -472,6 +472,66 @@ def test_main_core(name):
     assert len(plc().k_core(h, g, k + 1, None, None, False)[0]) == 0
 
 
+def distinct_weight(s, d):
+    """pair_weight's pattern with no two pairs alike; exact in fp32 for ids below 256."""
+    return 0.5 + np.minimum(s, d) * 256 + np.maximum(s, d)
+
+
+@functools.lru_cache(maxsize=None)
+def long_row_case(length):
+    """K_4 on 0..3 and length - 3 further vertices, each joined to 0 and to 1: row 0 has `length`
+    entries, 3 of them in the 3-core, and every vertex is in the 2-core."""
+    import networkx as nx
+    extra = np.arange(4, length + 1)
+    ks, kd = clique_edges(np.arange(4))
+    s, d = symmetrize(np.r_[ks, np.zeros_like(extra), np.ones_like(extra)], np.r_[kd, extra, extra])
+    case = Case(s, d, renumber=True, symmetrized=True, w=distinct_weight(s, d).astype(np.float32))
+    assert int((s == 0).sum()) == length and len(set(case.w.tolist())) == len(s) // 2
+    G = nx.Graph()
+    G.add_edges_from(zip(s.tolist(), d.tolist()))
+    for k, edges in ((2, (length - 3) * 2 + 6), (3, 6), (4, 0)):
+        want = nx.k_core(G, k).edges()
+        assert len(want) == edges
+        assert sorted([(a, b) for a, b in want] + [(b, a) for a, b in want]) == case.k_core_pairs(k)
+    return case
+
+
+@pytest.mark.parametrize("transposed", [False, True])
+@pytest.mark.parametrize("renumber", [True, False])
+@pytest.mark.parametrize("length", [63, 64, 65, 128, 129])
+def test_k_core_rows_at_the_wave_boundary(length, renumber, transposed):
+    """Row 0 is taken by a thread below 64 entries and by a wave from 64 on: kept whole (k = 2),
+    kept in 3 of its entries (k = 3), and dropped (k = 4); weights follow their entries."""
+    case = long_row_case(length).with_(renumber=renumber)
+    h, g = case.graph(transposed)
+    for k in (2, 3):
+        got = check_k_core(case, k, plc().k_core(h, g, k, None, None, False), weight_of=distinct_weight)
+        if not renumber:
+            assert got == sorted(got)  # by row, then by stored position: rows ascend
+    src, dst, w = plc().k_core(h, g, 4, None, None, False)
+    assert len(host(src)) == 0 and len(host(dst)) == 0 and host(src).dtype == np.int32
+    assert w is not None and len(host(w)) == 0 and host(w).dtype == np.float32
+
+
+def test_k_core_repeats_and_a_loop_in_a_wave_row():
+    """The 65-entry row stores one entry twice (the copies weigh differently) and a loop: each pair
+    comes back once, with the weight of its first stored copy, in the order of the rows."""
+    base = long_row_case(65)
+    s, d = np.r_[base.s, 0, 40, 0], np.r_[base.d, 40, 0, 0]
+    w = np.r_[base.w, -1.0, -2.0, -3.0].astype(np.float32)
+    case = Case(s, d, renumber=False, symmetrized=True, w=w)
+    h, g = case.graph()
+    off, idx, aw = (host(x) for x in g.adjacency(h, transposed=False))
+    assert off[1] - off[0] == 67 and sorted(idx[:67].tolist()) == sorted([0, 40] + list(range(1, 66)))
+    rows = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    first = {}
+    for r, c, x in zip(rows.tolist(), idx.tolist(), aw.tolist()):
+        first.setdefault((r, c), x)
+    got = check_k_core(case, 2, plc().k_core(h, g, 2, None, None, False),
+                       weight_of=lambda a, b: np.array([first[p] for p in zip(a.tolist(), b.tolist())], np.float32))
+    assert got == sorted(got) and len(got) == len(base.s)
+
+
 # ------------------------------------------------------------------ 8. refusals
 def test_asymmetric_graph_is_refused():
     h, g = make_graph([0, 1], [1, 2], None, symmetric=False)
