@@ -947,9 +947,13 @@ void bfs_impl(handle_t& h, graph_t& g, array_view_t* sources, bool dir_opt, size
                      res.vertices->buf.data<V>());
   CGX_LAUNCH_CHECK();
   dbuf<V> qa[3], qb[3];
+  // qb[0] also holds the probe's residual sub-queues (kCtrParts * residual_cap(nv) entries, up
+  // to 1023 more than nv); every top-down level that is not speculated swaps qa and qb,
+  // so either buffer can be the one the probe gets: both have that size
   for (int c = 0; c < 3; ++c) {
-    qa[c].resize(nv, s);
-    qb[c].resize(c == 0 ? std::max<int64_t>(nv, kCtrParts * residual_cap(nv)) : nv, s);  // qb[0]: residual sub-queues too
+    int64_t const cap = c == 0 ? std::max<int64_t>(nv, kCtrParts * residual_cap(nv)) : nv;
+    qa[c].resize(cap, s);
+    qb[c].resize(cap, s);
   }
   // ctr2: queue lengths of a bitmap -> queues conversion; ctr3: a speculative level's counters
   // one allocation and one memset for the three counter blocks; k_publish_seq

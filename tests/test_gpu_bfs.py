@@ -3,9 +3,9 @@ documented tie rule (smallest internal id), and valid per bfs_test.cpp:210-230."
 import numpy as np
 import pytest
 
+from bfs_cases import check_vs_oracle
 from conftest import dataset_path
 from gpu_util import host, make_graph, plc
-from oracle import bfs as obfs
 from oracle import graph as og
 from oracle import rmat
 
@@ -16,20 +16,6 @@ INT32_MAX = 2**31 - 1
 def run(h, G, sources, do, depth=0, pred=True, vdtype=np.int32):
     d, p, v = plc().bfs(h, G, np.asarray(sources, vdtype), do, depth, pred, False)
     return host(v), host(d), host(p)
-
-
-def check_vs_oracle(s, d, v, dist, pred, sources_ext, depth_limit=None, inf=INT32_MAX):
-    n_ext = int(max(np.max(s, initial=0), np.max(d, initial=0), np.max(sources_ext))) + 1
-    G = og.create_graph(s, d, None, renumber=False, vertices=np.arange(n_ext))
-    key = np.full(n_ext, np.iinfo(np.int64).max // 2, dtype=np.int64)
-    key[v] = np.arange(v.size)  # internal id = position in the result arrays
-    # make the key a permutation (ids absent from the GPU graph never win)
-    absent = np.setdiff1d(np.arange(n_ext), v)
-    key[absent] = v.size + np.arange(absent.size)
-    rd, rp = obfs.bfs(n_ext, G.offsets, G.indices, sources_ext, depth_limit, tie_key=key, invalid_distance=inf)
-    assert np.array_equal(dist, rd[v])
-    if pred is not None and pred.size:
-        assert np.array_equal(pred, rp[v])
 
 
 def test_c_golden(golden):
